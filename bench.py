@@ -11,6 +11,11 @@ One process per GPU, `--envs-per-gpu` envs each (weak scaling). The env path has
 is no collective on it (barrier + max-over-ranks timing only); `--gather` adds the optional centralised-learner
 exchange: the step outputs all-gathered over RCCL, in rollout chunks, inside the timed region.
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds what takes runs of its own: the
+HIP-event kernel time and the roofline blocks (a second, profiled region under the same protocol), the CPU baselines
+and, for N > 1, the other of the two exchange modes. `--dump-outputs DIR` writes what the last timed step returned
+(obs / reward / terminated / truncated / info) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +50,7 @@ VALU_PEAK_WAVE_INSTS_PER_S = 1024 * 2.4e9 / 2
 # ... but ONE wave alone on its SIMD sustains one VALU instruction per 4 cycles (the guide's per-instruction constants): the
 # control-step kernel takes the CU's whole register file and LDS, so it never has a second wave -- this is its attainable peak
 VALU_PEAK_ONE_WAVE_PER_SIMD = 1024 * 2.4e9 / 4
+PROFILE_LAUNCHES = 4096  # launches the library's event pool times between two profile reads (mssim_profile_enable)
 PROFILE_DIR = os.path.join(ROOT, "profiles", "round3")  # separate --pmc passes of this same command, scripts/collect_profiles.py
 
 
@@ -95,16 +101,18 @@ def protocol_of(args):
 
 
 def timed_steps(env, steps, gather, barrier):
+    """(seconds, what the last env.step returned)"""
     base = env.unwrapped
     dev = base.device
     N = base.num_envs
+    out = None
     barrier()
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(steps):
         a = 2 * torch.rand((N, 8), device=dev) - 1
-        obs, rew, term, trunc, info = env.step(a)
+        out = obs, rew, term, trunc, info = env.step(a)
         if gather is not None:
             gather.add(obs, rew, term | trunc)  # packed record into the rollout chunk; one RCCL all-gather per chunk
     if gather is not None:
@@ -113,7 +121,45 @@ def timed_steps(env, steps, gather, barrier):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(out):
+    """the step outputs as host arrays, float64 kept and everything else as float32; taken right after the timed region
+    (the fused step hands back views of buffers that the next step overwrites)"""
+    obs, rew, term, trunc, info = out
+    named = {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc}
+
+    def walk(prefix, d):
+        for k, v in d.items():
+            if isinstance(v, dict):
+                walk(f"{prefix}{k}_", v)
+            elif torch.is_tensor(v):
+                named[f"{prefix}{k}"] = v
+
+    walk("info_", info)
+    return {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy() for k, v in named.items()}
+
+
+def dump_outputs(out_dir, arrays, n, limit, prefix=""):
+    """DIR/<prefix><name>.npy per array. Above `limit` bytes in all, a fixed seeded sample of the env rows is written
+    instead, the same rows in every per-env array, and their indices go to <prefix>sample_rows.npy."""
+    import numpy as np
+
+    per_env = {k for k, a in arrays.items() if a.ndim >= 1 and a.shape[0] == n}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit and per_env:
+        fixed = sum(a.nbytes for k, a in arrays.items() if k not in per_env)
+        row_bytes = sum(arrays[k].nbytes for k in per_env) / n  # (+ 8 below: the row's index in sample_rows)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=max(1, int((limit - fixed) // (row_bytes + 8))), replace=False))
+        arrays = {k: (a[rows] if k in per_env else a) for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{prefix}{k}.npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(seconds_budget=20.0):
@@ -175,11 +221,17 @@ def main():
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
     ap.add_argument("--control-freq", type=int, default=20, help="sim_freq is 100: 20 -> 5 substeps (reference default), 25 -> 4")
     ap.add_argument("--env-id", default="PickCube-v1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: kernel time + roofline blocks (a second, profiled timed region), CPU "
+                         "baselines, and for --gpus > 1 the other exchange mode. Off by default: a plain run times the K steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all; "
+                         "ranks > 0 prefix rank<r>_), e.g. DIR = bench_outputs/")
     ap.add_argument("--gather", action="store_true",
                     help="centralised-learner mode: all-gather obs/reward/done over RCCL inside the timed region (--gpus > 1). Off by "
                          "default: the env path has no exchange step, every rank's learner shard consumes its own envs")
-    ap.add_argument("--no-gather", action="store_true", help="(default behaviour; kept for older command lines)")
+    ap.add_argument("--no-gather", action="store_true", help="with --full and --gpus > 1: skip the second (gathered) timed region")
     ap.add_argument("--gather-every", type=int, default=8, help="control steps per all-gather (rollout chunk) when --gpus > 1")
     args = ap.parse_args()
 
@@ -249,10 +301,11 @@ def main():
     base = env.unwrapped
     seeds = shard_seeds(global_seeds, rank, world)
     obs, _ = env.reset(seed=seeds)
-    # N > 1: two timed regions of K steps each, back to back -- (1) the env path as it is (no collective: `value`),
-    # (2) the centralised-learner exchange of BASELINE config 4 on top (RCCL all-gather of obs / reward / done over xGMI
-    # in rollout chunks: `gathered`). `--gather` makes (2) the headline instead; `--no-gather` skips (2).
+    # N > 1: (1) the env path as it is (no collective: `value`), (2) the centralised-learner exchange of BASELINE config 4
+    # on top (RCCL all-gather of obs / reward / done over xGMI in rollout chunks: `gathered`). `--gather` makes (2) the
+    # headline instead. `--full` times the other one too, in a second region of K steps; `--no-gather` skips (2) there.
     gather = RolloutGather(n, obs.shape[1], dev, chunk=args.gather_every) if (world > 1 and not args.no_gather) else None
+    gather_headline = args.gather and gather is not None
 
     def warmup(g):
         for _ in range(args.warmup):
@@ -271,30 +324,31 @@ def main():
         return float(t.item())
 
     px = base.scene.px
-    warmup(None)
-    px.profile_enable(True)
-    elapsed = max_over_ranks(timed_steps(env, args.steps, None, barrier))
-    prof = px.profile_read()
-    px.profile_enable(False)
+    warmup(gather if gather_headline else None)
+    elapsed, last = timed_steps(env, args.steps, gather if gather_headline else None, barrier)
+    elapsed = max_over_ranks(elapsed)
     overflow = px.overflow_count()
-    elapsed_gathered = None
-    if gather is not None:
-        warmup(gather)
-        elapsed_gathered = max_over_ranks(timed_steps(env, args.steps, gather, barrier))
-        if args.gather:
-            elapsed, elapsed_gathered = elapsed_gathered, elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, host_outputs(last), n, DUMP_LIMIT_BYTES // world, "" if rank == 0 else f"rank{rank}_")
+    last = None
+    elapsed_other = None
+    if args.full and gather is not None:
+        warmup(None if gather_headline else gather)
+        elapsed_other = max_over_ranks(timed_steps(env, args.steps, None if gather_headline else gather, barrier)[0])
+    prof = None
+    if args.full:
+        # the kernel's own time: HIP events around every launch, in a region of its own under the headline's protocol
+        # (same action stream, fresh episodes after the same warm-up), so the headline region carries no events
+        torch.manual_seed(2022 + rank)
+        warmup(None)
+        px.profile_enable(True)
+        timed_steps(env, args.steps, None, barrier)
+        prof = px.profile_read()
+        px.profile_enable(False)
 
     if rank == 0:
         total_envs = n * world
         value = args.steps * total_envs / elapsed
-        solve_ms, solve_n = prof["solve"]
-        narrow_ms, narrow_n = prof["narrow"]
-        avg_solve_s = (solve_ms / max(solve_n, 1)) * 1e-3
-        assert solve_n == args.steps and narrow_n == 0, (solve_n, narrow_n)  # one launch = n envs x one control step
-        alg_bytes_per_launch = ALG_BYTES_PER_ENV_STEP * n
-        kernel_name, kernel_key = f"k_solve16<NDOF, TASK> (whole env.step in one launch: action map, {substeps} substeps incl. narrowphase + contact patches, copy-out, task epilogue; 16 lanes/env)", "k_solve16<"
-        achieved = alg_bytes_per_launch / avg_solve_s / 1e9 if avg_solve_s > 0 else 0.0
-        traffic, traffic_raw, valu_insts = committed_counters(kernel_key, protocol_of(args))
         out = {
             "metric": "env-steps/sec (whole node), PickCube-v1 state-obs 4096 envs/GPU",
             "value": round(value, 1),
@@ -313,10 +367,21 @@ def main():
                 "15+1 solver iterations, random actions 2*U-1, no resets inside the timed region",
                 "envs_per_gpu": n,
                 "substeps": substeps,
-                "parallelism": f"env-sharded x{world}" + (", headline = centralised-learner mode (all-gather inside the timed region)" if (args.gather and gather is not None) else ", no collective on the env path"),
+                "parallelism": f"env-sharded x{world}" + (", headline = centralised-learner mode (all-gather inside the timed region)" if gather_headline else ", no collective on the env path"),
                 "solver_overflow_envs": overflow,
             },
-            "roofline": {
+        }
+        if prof is not None:
+            solve_ms, solve_n = prof["solve"]
+            narrow_ms, narrow_n = prof["narrow"]
+            avg_solve_s = (solve_ms / max(solve_n, 1)) * 1e-3
+            # one launch = n envs x one control step (the library records the first PROFILE_LAUNCHES launches)
+            assert solve_n == min(args.steps, PROFILE_LAUNCHES) and narrow_n == 0, (solve_n, narrow_n)
+            alg_bytes_per_launch = ALG_BYTES_PER_ENV_STEP * n
+            kernel_name, kernel_key = f"k_solve16<NDOF, TASK> (whole env.step in one launch: action map, {substeps} substeps incl. narrowphase + contact patches, copy-out, task epilogue; 16 lanes/env)", "k_solve16<"
+            achieved = alg_bytes_per_launch / avg_solve_s / 1e9 if avg_solve_s > 0 else 0.0
+            traffic, traffic_raw, valu_insts = committed_counters(kernel_key, protocol_of(args))
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": kernel_name,
                 "achieved": round(achieved, 4),
@@ -330,9 +395,9 @@ def main():
                 "avg_kernel_ms": round(avg_solve_s * 1e3, 4),
                 "launches": solve_n,
                 "algorithmic_bytes_per_launch": alg_bytes_per_launch,
-            },
+            }
             # the bound that applies (neither HBM nor MFMA): vector-instruction issue
-            "roofline_valu": {
+            out["roofline_valu"] = {
                 "bound": "valu-issue",
                 "achieved": None if valu_insts is None or avg_solve_s <= 0 else round(valu_insts / avg_solve_s / 1e12, 4),
                 "peak": VALU_PEAK_WAVE_INSTS_PER_S / 1e12,
@@ -341,21 +406,20 @@ def main():
                 "peak_one_wave_per_simd": VALU_PEAK_ONE_WAVE_PER_SIMD / 1e12,
                 "frac_of_one_wave_peak": None if valu_insts is None or avg_solve_s <= 0 else valu_insts / avg_solve_s / VALU_PEAK_ONE_WAVE_PER_SIMD,
                 "wave_valu_instructions_per_launch": valu_insts,
-                "source": "SQ_INSTS_VALU from profiles/round3/sq_counters.json (same source-hash and protocol rule) / HIP-event kernel time of this run; `peak`: one wave64 "
+                "source": "SQ_INSTS_VALU from profiles/round3/sq_counters.json (same source-hash and protocol rule) / HIP-event kernel time of this run's profiled region; `peak`: one wave64 "
                           "instruction per 2 cycles and SIMD (chip), `peak_one_wave_per_simd`: per 4 cycles -- what a kernel at one wave per SIMD, as this one, can reach",
-            },
-        }
-        if elapsed_gathered is not None:
-            other = "no collective" if args.gather else f"one packed RCCL all-gather of obs / reward / done per {args.gather_every} control steps (asynchronous, overlaps the next chunk), inside the timed region"
-            out["gathered" if not args.gather else "ungathered"] = {
-                "value": round(args.steps * total_envs / elapsed_gathered, 1),
+            }
+        if elapsed_other is not None:
+            other = "no collective" if gather_headline else f"one packed RCCL all-gather of obs / reward / done per {args.gather_every} control steps (asynchronous, overlaps the next chunk), inside the timed region"
+            out["ungathered" if gather_headline else "gathered"] = {
+                "value": round(args.steps * total_envs / elapsed_other, 1),
                 "unit": "env-steps/s",
-                "ms_per_step": round(elapsed_gathered / args.steps * 1e3, 4),
+                "ms_per_step": round(elapsed_other / args.steps * 1e3, 4),
                 "what": f"second timed region of {args.steps} steps in the same run: {other}",
             }
         if rehearse:
             out["rehearsal"] = f"{world} ranks sharing one GPU (MSSIM_BENCH_REHEARSE=1): the multi-rank code path, not a measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             env.close()
             try:
                 out["cpu_baseline"] = cpu_baseline()

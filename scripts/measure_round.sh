@@ -9,7 +9,7 @@ O=$PWD/gpurun_out
 P=/tmp/mssim_prof   # raw rocprofv3 output stays on the box (tens of MB per pass); only the summaries travel back
 mkdir -p "$O"
 rm -rf "$P" "$O"/stats "$O"/stats20 "$O"/pmc_fetch "$O"/pmc_write "$O"/pmc_sq "$O"/pmc_ic; mkdir -p "$P"
-echo "== bench (default flags: 1000 steps)"; python3 bench.py > "$O"/bench.json.log 2> "$O"/bench.err || exit 1
+echo "== bench --full (default flags: 1000 steps)"; python3 bench.py --full > "$O"/bench.json.log 2> "$O"/bench.err || exit 1
 tail -c 600 "$O"/bench.json.log
 echo "== kernel stats"; (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$P"/stats -- python3 "$OLDPWD"/bench.py --no-cpu-baseline > "$O"/bench_prof.log 2>&1) || exit 1
 # (and of the command the driver's round-end run uses: 20 steps over fresh episodes)

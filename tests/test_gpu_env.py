@@ -10,6 +10,16 @@ pytestmark = pytest.mark.gpu
 BACKEND = "physx_cuda"
 
 
+@pytest.fixture
+def pinned_torch_rng():
+    """an unseeded env.reset() draws the new episodes from torch's ambient stream (as the reference's does), and that
+    stream's seed differs from process to process: pinned for the test, so that a rollout with such resets is the same
+    rollout in every run"""
+    with torch.random.fork_rng():
+        torch.manual_seed(0)
+        yield
+
+
 def test_shapes_and_devices():
     ec.check_shapes_and_devices(BACKEND, "cuda")
 
@@ -298,7 +308,7 @@ def test_yaw_only_random_quaternions_equal_the_generic_route_on_device():
 
 
 @pytest.mark.parametrize("env_id,control_mode", [("PickCube-v1", "pd_ee_delta_pose"), ("PegInsertionSide-v1", "pd_ee_delta_pos"), ("PegInsertionSide-v1", "pd_joint_delta_pos")])
-def test_abusive_rollouts_stay_bounded(env_id, control_mode):
+def test_abusive_rollouts_stay_bounded(env_id, control_mode, pinned_torch_rng):
     """random end-effector pushes drive the arm through singular poses (IK steps of tens of radians), into the table
     and against the peg: 600 control steps with full and partial resets stay finite and bounded -- the regime that
     exposed the unbounded spin of thin bodies, the unbounded joint velocities and the f32 cancellation of saturated
@@ -415,7 +425,7 @@ def test_fused_epilogue_follows_controller_switches_and_hidden_objects():
     env.close()
 
 
-def test_peg_insertion_has_no_contact_overflow():
+def test_peg_insertion_has_no_contact_overflow(pinned_torch_rng):
     """BASELINE config 3 (PegInsertionSide-v1, 2048 envs): 600 random control steps without one env above the contact
     capacity (round 1: ~28 % of the envs above it). The finger boxes against the boxes of the hole produce up to 100+
     raw manifold points per env; the contact patches of a body pair (include/mssim.h MSSIM_PATCH_COS) keep 4 each."""
