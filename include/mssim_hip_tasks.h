@@ -1,0 +1,52 @@
+/* mssim_hip_tasks.h -- task epilogues of the HIP library only (libmssim.so), outside the core ABI of mssim.h.
+ *
+ * mssim.h is the contract both implementations export (the HIP library and the CPU oracle, every MSSIM_FN of it under
+ * its own prefix). The entry points below exist in the HIP library alone: plain extern "C" symbols, bound by
+ * maniskill_amd/native.py as optional extras. They follow the conventions of the task_*_outputs calls of mssim.h
+ * (device pointers, the caller's stream, no host sync; a deferred step_action + fetch makes the whole control step
+ * one launch). */
+#ifndef MSSIM_HIP_TASKS_H
+#define MSSIM_HIP_TASKS_H
+
+#include "mssim.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* StackCube-style evaluate + state observation + dense reward in one launch
+ * (envs/tasks/tabletop/stack_cube.py, agents/robots/panda/panda.py is_grasping). Reads the user-visible buffers (after
+ * fetch) and the last substep's contact impulses.
+ * obs [N][2*n_dof+30] f32 (qpos, qvel, tcp_pose7, cubeA_pose7, cubeB_pose7, tcp_to_cubeA3, tcp_to_cubeB3, cubeA_to_cubeB3),
+ * reward [N] f32, flags [N][4] u8 = success, is_cubeA_on_cubeB, is_cubeA_static, is_cubeA_grasped.
+ * The struct is no larger than mssim_peg_task (the control-step kernel carries every task struct in one union). */
+typedef struct mssim_stack_task {
+  int32_t tcp_row, cubeA_row, cubeB_row, finger1_row, finger2_row; /* rigid_body_data body rows */
+  float cube_half_size;       /* 0.02: A is on B when |dz - 2 half| <= on_z_thresh ...                              */
+  float on_xy_thresh;         /* ... and |dxy| <= this (|half_xy| + 0.005, as evaluate() computes it in f32)        */
+  float on_z_thresh;          /* 0.005 */
+  float gripper_width;        /* upper limit of the last finger joint x 2 (ungrasp reward = finger gap / this)         */
+  float static_lin_thresh;    /* 1e-2 m/s   (Actor.is_static of cube A)                                              */
+  float static_ang_thresh;    /* 0.5 rad/s                                                                           */
+  float min_force;            /* 0.5 N  (is_grasping of cube A)                                                      */
+  float max_angle_deg;        /* 85                                                                                  */
+  float reward_scale;         /* 1 (dense) or 1/8 (normalized_dense)                                                 */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;     /* optional device [N]: new elapsed_steps >= time_limit */
+  int32_t time_limit;
+  uint8_t* terminated_out;    /* optional device [N]: a copy of success */
+} mssim_stack_task;
+
+int mssim_task_stack_outputs(mssim_handle h, const mssim_stack_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
+
+/* How many control steps of this handle so far ran as one launch with a task epilogue at the control-step kernel's
+ * tail (a deferred step_action + fetch consumed by a task_*_outputs call), against the separate epilogue launch.
+ * A host counter: no sync. */
+int64_t mssim_tail_step_count(mssim_handle h);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MSSIM_HIP_TASKS_H */

@@ -24,7 +24,12 @@
 #include <vector>
 
 #include "../../include/mssim.h"
+#include "../../include/mssim_hip_tasks.h"
 #include "mssim_collide.h"
+
+// the control-step kernel carries the task structs in one union (DevState::tail_task): a new one must not widen it,
+// or the kernel arguments of every instance change
+static_assert(sizeof(mssim_stack_task) <= sizeof(mssim_peg_task) && alignof(mssim_stack_task) <= alignof(mssim_peg_task), "tail_task union would grow");
 
 #define MAXC 52  // solver blocks per env: contact points + torsional blocks (overflow is reported, never silent); 4 envs x the LDS tables = 40.0 KB per block, 4 blocks per CU
 
@@ -81,7 +86,7 @@ struct DevState {
   // copy-out + task epilogue at the tail of the fused launch (whole control step = one launch); 0 = none
   unsigned tail_fetch;                          // mssim_fetch mask
   mssim_buffers tail_buf;
-  union { mssim_pick_task pick; mssim_push_task push; mssim_peg_task peg; } tail_task;  // kind = template TASK
+  union { mssim_pick_task pick; mssim_push_task push; mssim_peg_task peg; mssim_stack_task stack; } tail_task;  // kind = template TASK
   const int* tail_pairs; int tail_npairs;       // finger <-> object candidate pairs
   float *tail_obs, *tail_reward, *tail_head;
   uint8_t* tail_flags;
@@ -730,6 +735,80 @@ __global__ __launch_bounds__(256) void k_task_peg(DevModel M, DevState S, mssim_
   task_peg_env(M, S, B, T, pairs, npairs, obs, reward, flags, head_out, e);
 }
 
+// StackCube evaluate / obs / reward (stack_cube.py evaluate, _get_obs_extra, compute_dense_reward)
+MS_DEV void task_stack_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_stack_task& T, const int* __restrict__ pairs, int npairs,
+                           float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 30);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  for (int j = 0; j < n; j++) {
+    o[j] = B.art_qpos[(size_t)e * n + j];
+    o[n + j] = B.art_qvel[(size_t)e * n + j];
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* ca = rowp(T.cubeA_row);
+  const float* cb = rowp(T.cubeB_row);
+  const f3 ptcp = f3{tcp[0], tcp[1], tcp[2]}, pa = f3{ca[0], ca[1], ca[2]}, pb = f3{cb[0], cb[1], cb[2]};
+  // finger <-> cube A contact forces of the last substep (Panda.is_grasping, as task_pick_env)
+  f3 lf = f3{0, 0, 0}, rf = f3{0, 0, 0};
+  for (int k = 0; k < npairs; k++) {
+    const unsigned ent = (unsigned)pairs[k];
+    const int p = (int)(ent & 0x3FFFFFFFu);
+    if (S.pair_cnt[(size_t)p * N + e] <= 0) continue;
+    f3 imp = f3{SOA(S.pair_imp, 3 * p), SOA(S.pair_imp, 3 * p + 1), SOA(S.pair_imp, 3 * p + 2)} * ((ent >> 31) ? -1.f : 1.f);
+    if ((ent >> 30) & 1u) rf += imp; else lf += imp;
+  }
+  const float inv_dt = 1.f / M.dt;
+  lf = lf * inv_dt; rf = rf * inv_dt;
+  auto yaxis = [&](const float* r) { return mcol(qmat(qnormalized(q4{r[3], r[4], r[5], r[6]})), 1); };
+  auto angle_deg = [&](f3 a, f3 b) {
+    const float na = norm(a), nb = norm(b);
+    a = a * (1.f / (na < 1e-6f ? 1.f : na));
+    b = b * (1.f / (nb < 1e-6f ? 1.f : nb));
+    return acosf(fminf(fmaxf(dot(a, b), -1.f), 1.f)) * 57.29577951308232f;
+  };
+  const f3 ldir = yaxis(rowp(T.finger1_row)), rdir = -yaxis(rowp(T.finger2_row));
+  const bool grasped = norm(lf) >= T.min_force && angle_deg(ldir, lf) <= T.max_angle_deg && norm(rf) >= T.min_force && angle_deg(rdir, rf) <= T.max_angle_deg;
+  // evaluate
+  const f3 off = pa - pb;
+  const bool on = sqrtf(off.x * off.x + off.y * off.y) <= T.on_xy_thresh && fabsf(off.z - T.cube_half_size * 2.f) <= T.on_z_thresh;
+  const f3 va = f3{ca[7], ca[8], ca[9]}, wa = f3{ca[10], ca[11], ca[12]};
+  const float v = norm(va), av = norm(wa);
+  const bool is_static = v <= T.static_lin_thresh && av <= T.static_ang_thresh;
+  const bool success = on && is_static && !grasped;
+  // observation
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  for (int i = 0; i < 7; i++) o[k++] = ca[i];
+  for (int i = 0; i < 7; i++) o[k++] = cb[i];
+  o[k++] = pa.x - ptcp.x; o[k++] = pa.y - ptcp.y; o[k++] = pa.z - ptcp.z;
+  o[k++] = pb.x - ptcp.x; o[k++] = pb.y - ptcp.y; o[k++] = pb.z - ptcp.z;
+  o[k++] = pb.x - pa.x; o[k++] = pb.y - pa.y; o[k++] = pb.z - pa.z;
+  // dense reward, tiered: reach A, A grasped (+ place), A on B (+ ungrasp, static), success
+  float r = 2.f * (1.f - tanhf(5.f * norm(ptcp - pa)));
+  if (grasped) r = 4.f + (1.f - tanhf(5.f * norm(f3{pb.x, pb.y, pb.z + T.cube_half_size * 2.f} - pa)));
+  if (on) {
+    const float ungrasp = grasped ? (B.art_qpos[(size_t)e * n + n - 2] + B.art_qpos[(size_t)e * n + n - 1]) / T.gripper_width : 1.f;
+    r = 6.f + (ungrasp + (1.f - tanhf(v * 10.f + av))) / 2.f;
+  }
+  if (success) r = 8.f;
+  reward[e] = r * T.reward_scale;
+  uint8_t* f = flags + 4 * (size_t)e;
+  f[0] = success; f[1] = on; f[2] = is_static; f[3] = grasped;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_stack(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_stack_task T, const int* __restrict__ pairs, int npairs,
+                                                     float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_stack_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
+}
+
 // geometric Jacobian of link `link` in the root frame: out [N][6][n_dof] (see include/mssim.h)
 __global__ void k_link_jacobian(DevModel M, DevState S, int link, float* __restrict__ out) {
   const int N = S.N;
@@ -792,6 +871,7 @@ struct mssim_sim {
   std::vector<float> h_dof_pack; float* d_dof_pack = nullptr;  // (drive gains are patched by set_drive_properties)
   std::vector<int32_t> h_shape_row, h_pair_shape;  // host copies (contact-pair lists of the task epilogues)
   int* d_pick_pairs = nullptr; int n_pick_pairs = 0; int pick_rows[3] = {-1, -1, -1};
+  long long n_tail_steps = 0;  // control steps that ran with the task epilogue at the kernel's tail (mssim_tail_step_count)
   std::vector<int*> queries;
   std::vector<int> query_n;
   std::vector<int> query_kind;
@@ -1312,7 +1392,8 @@ int mssim_step(mssim_handle h, int32_t n_substeps, void* stream) {
   return 0;
 }
 
-// TASK: 0 = plain control step, 1 / 2 / 3 = copy-out + PickCube / PushCube / PegInsertionSide epilogue at its tail
+// TASK: 0 = plain control step, 1 / 2 / 3 = copy-out + PickCube / PushCube / PegInsertionSide epilogue at its tail (one row per
+// env), 4 = copy-out + StackCube epilogue (two rows per env: the Panda with two cubes)
 extern "C++" {
 template <int TASK>
 static void launch_control_step(mssim_handle h, const DevState& S, int n_substeps, hipStream_t st) {
@@ -1320,7 +1401,8 @@ static void launch_control_step(mssim_handle h, const DevState& S, int n_substep
   const dim3 block(64 * S16_WAVES);
 #ifdef MSSIM_ONLY_PANDA
   // (timing experiments, scripts/ab_variants.sh: only the benchmark's instances are compiled -- a fifth of the build time)
-  hipLaunchKernelGGL((k_solve16<9, TASK>), env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK), block, 0, st, h->M, S, n_substeps);
+  // (TASK 4 is not among them: control_step_with_task leaves StackCube to the separate epilogue launch in this build)
+  hipLaunchKernelGGL((k_solve16<9, TASK == 4 ? 0 : TASK>), env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK), block, 0, st, h->M, S, n_substeps);
 #else
   if (h->rows_per_env == 4) {  // three to six free bodies: four 16-lane rows (a whole wave) per env, 4 envs per block; the generic-topology instances
     const dim3 grid4 = env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK / 4);
@@ -1335,7 +1417,10 @@ static void launch_control_step(mssim_handle h, const DevState& S, int n_substep
       if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, 0, true, 2>), grid2, block, 0, st, h->M, S, n_substeps);
       else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0, true, 2>), grid2, block, 0, st, h->M, S, n_substeps);
       else hipLaunchKernelGGL((k_solve16<0, 0, true, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-    } else if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, 0, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
+    } else if (h->M.n_dof == 9) {
+      if (TASK == 4) hipLaunchKernelGGL((k_solve16<9, 4, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
+      else hipLaunchKernelGGL((k_solve16<9, 0, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
+    }
     else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
     else hipLaunchKernelGGL((k_solve16<0, 0, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
     prof_mark(h, 0, st);
@@ -1346,7 +1431,7 @@ static void launch_control_step(mssim_handle h, const DevState& S, int n_substep
     if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
     else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
     else hipLaunchKernelGGL((k_solve16<0, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
-  } else if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, TASK>), grid, block, 0, st, h->M, S, n_substeps);
+  } else if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, TASK == 4 ? 0 : TASK>), grid, block, 0, st, h->M, S, n_substeps);
   else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0>), grid, block, 0, st, h->M, S, n_substeps);  // (the Fetch)
   else hipLaunchKernelGGL((k_solve16<0, 0>), grid, block, 0, st, h->M, S, n_substeps);
 #endif
@@ -1503,15 +1588,24 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
 }
 
 // A deferred step_action + deferred fetch + this epilogue = one launch of the control-step kernel (Panda
-// models: the task tail is compiled into k_solve16<9, TASK>). Returns false if that does not apply.
+// models: the task tail is compiled into k_solve16<9, TASK> for one row per env, k_solve16<9, 4, false, 2> for
+// StackCube's two). Returns false if that does not apply.
 extern "C++" {
 template <int TASK>
 static bool control_step_with_task(mssim_handle h, DevState& S, hipStream_t st) {
-  if (!(h->deferred_action && h->deferred_fetch && h->M.n_dof == 9 && h->deferred_nsub > 0 && st == h->deferred_stream && h->ee.link < 0) || h->has_tri || h->rows_per_env != 1) return false;
+  if (!(h->deferred_action && h->deferred_fetch && h->M.n_dof == 9 && h->deferred_nsub > 0 && st == h->deferred_stream && h->ee.link < 0) || h->has_tri) return false;
+  const int rows = TASK == 4 ? 2 : 1;  // the rows per env the task's tail is compiled for
+#ifdef MSSIM_ONLY_PANDA
+  if (rows != 1) return false;  // (only the one-row instances are compiled)
+#endif
+  if (h->rows_per_env != rows) return false;
   // The tail runs at the kernel's one wave per SIMD: worth it while all blocks are resident at once (4 per CU) and
   // the launch is latency-bound anyway; with more blocks the separate, fully occupied copy-out + epilogue launch
   // is cheaper than a tail per block.
-  if ((h->N + S16_ENVS_PER_BLOCK - 1) / S16_ENVS_PER_BLOCK > 4 * h->n_cu) return false;
+  if (rows == 1 && (h->N + S16_ENVS_PER_BLOCK - 1) / S16_ENVS_PER_BLOCK > 4 * h->n_cu) return false;
+  // Two rows: blocks of 8 envs, the same count of blocks (N <= 8192 on 256 CUs). Measured (StackCube, 4096 envs, 1000
+  // unreset steps): 0.947 ms per step with the tail, 0.963 ms with the separate launch.
+  if (rows == 2 && (h->N + 7) / 8 > 4 * h->n_cu) return false;
   const DevState A = state_with_action(h, h->deferred_action, h->deferred_adim);
   S.act = A.act; S.act_dim = A.act_dim; S.act_col = A.act_col; S.act_lo = A.act_lo; S.act_hi = A.act_hi; S.act_flags = A.act_flags;
   S.act_qpos = A.act_qpos; S.act_target = A.act_target; S.act_target_vel = A.act_target_vel;
@@ -1520,6 +1614,7 @@ static bool control_step_with_task(mssim_handle h, DevState& S, hipStream_t st) 
   h->deferred_action = nullptr;
   if (h->dirty) { launch_fk(h, st); h->dirty = false; }
   launch_control_step<TASK>(h, S, h->deferred_nsub, st);
+  h->n_tail_steps++;
   return true;
 }
 }  // extern "C++"
@@ -1546,6 +1641,31 @@ int mssim_task_peg_outputs(mssim_handle h, const mssim_peg_task* task, float* ob
   HIPCHK(h, hipGetLastError());
   return 0;
 }
+
+int mssim_task_stack_outputs(mssim_handle h, const mssim_stack_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
+  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
+  const int rows[5] = {task->tcp_row, task->cubeA_row, task->cubeB_row, task->finger1_row, task->finger2_row};
+  for (int r : rows)
+    if (r < 0 || r >= R) { h->err = "task_stack_outputs: body row out of range"; return 1; }
+  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
+  if (h->M.n_dof < 2 || !(task->gripper_width > 0.f)) { h->err = "task_stack_outputs: needs two finger joints and a gripper width > 0"; return 3; }
+  { int rc = finger_pair_list(h, task->cubeA_row, task->finger1_row, task->finger2_row); if (rc) return rc; }
+  {
+    DevState S = h->S;
+    S.tail_task.stack = *task; S.tail_pairs = h->d_pick_pairs; S.tail_npairs = h->n_pick_pairs;
+    S.tail_obs = obs; S.tail_reward = reward; S.tail_flags = flags; S.tail_head = nullptr;
+    if (control_step_with_task<4>(h, S, (hipStream_t)stream)) { HIPCHK(h, hipGetLastError()); return 0; }
+  }
+  if (h->deferred_action) { const unsigned w = take_deferred_fetch(h); flush_deferred(h, (hipStream_t)stream); h->deferred_fetch = w; }
+  if (const unsigned what = take_deferred_fetch(h))
+    hipLaunchKernelGGL(k_task_stack<true>, env_grid(h->N, 64), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
+  else
+    hipLaunchKernelGGL(k_task_stack<false>, env_grid(h->N, 64), dim3(64), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int64_t mssim_tail_step_count(mssim_handle h) { return h ? h->n_tail_steps : -1; }
 
 int mssim_task_pick_outputs(mssim_handle h, const mssim_pick_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
   const int R = h->M.n_link + h->M.n_free + h->M.n_kin;

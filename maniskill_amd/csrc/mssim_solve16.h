@@ -748,14 +748,14 @@ struct SupCoop16 {
 // NDOF > 0: the number of joints is a compile-time constant (9 for the Panda), so the loops over the
 // joints are unrolled and their masks folded; NDOF = 0 reads it from the model.
 // TASK > 0 (with FUSED): the launch ends with the copy-out (mssim_fetch) of its envs and the evaluate / obs /
-// reward epilogue of a task -- 1 PickCube, 2 PushCube, 3 PegInsertionSide -- so that a whole control step
-// (action map, substeps, copy-out, epilogue) is one launch.
+// reward epilogue of a task -- 1 PickCube, 2 PushCube, 3 PegInsertionSide (one row per env), 4 StackCube (two rows) -- so
+// that a whole control step (action map, substeps, copy-out, epilogue) is one launch.
 // TRI: the model has triangle-mesh shapes (MSSIM_SHAPE_TRIMESH): the narrowphase carries the mesh stage (BVH traversal, one
 // multi-point manifold per triangle in range); instantiated without a task tail only.
 template <int NDOF = 0, int TASK = 0, bool TRI = false, int NR = 1>
 __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState S, int n_sub) {
   constexpr bool FUSED = true;  // (the per-substep variant fed by a separate narrowphase kernel is gone)
-  static_assert(NR == 1 || ((NR == 2 || NR == 4) && TASK == 0), "rows per env: 1, 2 or 4; the task tails are compiled for one row only");
+  static_assert(NR == 1 || ((NR == 2 || NR == 4) && (TASK == 0 || (NR == 2 && TASK == 4))), "rows per env: 1, 2 or 4; the task tails: one row, and StackCube on two");
   constexpr int EPW = 4 / NR;                 // envs per wave
   constexpr int BLK_ENVS = S16_WAVES * EPW;   // envs per block
   constexpr int BLK_GRPS = S16_WAVES * 4;     // 16-lane groups per block: who takes the tasks of the shared narrowphase stages
@@ -3168,16 +3168,17 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
     // stores keep current): a block-scope fence = wait for the stores. (A device-scope fence would write back and
     // invalidate caches -- tens of microseconds per wave here.)
     __threadfence_block();
-    if (live) {
+    if (live) {  // (the env's GW lanes share its rows; all of them are in this wave)
       const int R = M.n_link + M.n_free + M.n_kin;
-      for (int row = c; row < R; row += 16) fetch_row(M, S, S.tail_buf, S.tail_fetch, e, row);
+      for (int row = cl; row < R; row += GW) fetch_row(M, S, S.tail_buf, S.tail_fetch, e, row);
       if (art) fetch_art_joint(M, S, S.tail_buf, S.tail_fetch, e, c);
     }
     __threadfence_block();
-    if (live && c == 0) {
+    if (live && cl == 0) {
       if (TASK == 1) task_pick_env(M, S, S.tail_buf, S.tail_task.pick, S.tail_pairs, S.tail_npairs, S.tail_obs, S.tail_reward, S.tail_flags, e);
       if (TASK == 2) task_push_env(M, S, S.tail_buf, S.tail_task.push, S.tail_obs, S.tail_reward, S.tail_flags, e);
       if (TASK == 3) task_peg_env(M, S, S.tail_buf, S.tail_task.peg, S.tail_pairs, S.tail_npairs, S.tail_obs, S.tail_reward, S.tail_flags, S.tail_head, e);
+      if (TASK == 4) task_stack_env(M, S, S.tail_buf, S.tail_task.stack, S.tail_pairs, S.tail_npairs, S.tail_obs, S.tail_reward, S.tail_flags, e);
     }
     PH(8);
   }

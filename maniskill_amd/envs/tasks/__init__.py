@@ -1,2 +1,2 @@
-from .tabletop import PegInsertionSideEnv, PickCubeEnv, PushCubeEnv
+from .tabletop import PegInsertionSideEnv, PickCubeEnv, PushCubeEnv, StackCubeEnv
 from .empty_env import EmptyEnv

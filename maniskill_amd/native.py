@@ -151,6 +151,15 @@ class PegTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class StackTask(C.Structure):
+    """mssim_stack_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("cubeA_row", C.c_int32), ("cubeB_row", C.c_int32), ("finger1_row", C.c_int32), ("finger2_row", C.c_int32),
+                ("cube_half_size", C.c_float), ("on_xy_thresh", C.c_float), ("on_z_thresh", C.c_float), ("gripper_width", C.c_float),
+                ("static_lin_thresh", C.c_float), ("static_ang_thresh", C.c_float), ("min_force", C.c_float), ("max_angle_deg", C.c_float),
+                ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -205,6 +214,17 @@ class NativeLib:
         f("abi_version", C.c_int, [])
         if self.abi_version() != ABI_VERSION:
             raise NativeError(f"{path}: ABI version {self.abi_version()} != {ABI_VERSION}")
+        # extras of the HIP library alone (include/mssim_hip_tasks.h), outside the ABI that the oracle shares: bound
+        # when present, None otherwise
+        H = C.c_void_p
+        for name, restype, argtypes in (
+            ("task_stack_outputs", C.c_int, [H, C.POINTER(StackTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("tail_step_count", C.c_int64, [H]),
+        ):
+            if hasattr(self.lib, self.prefix + name):
+                self._fn(name, restype, argtypes)
+            else:
+                setattr(self, name, None)
 
     EXPORTS = [
         "create", "destroy", "bind_buffers", "set_timestep", "get_timestep", "apply", "fetch", "step",
@@ -349,6 +369,17 @@ class NativeSim:
 
     def task_push_outputs(self, task: "PushTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
         self._check(self.lib.task_push_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_push_outputs")
+
+    def task_stack_outputs(self, task: "StackTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
+        if self.lib.task_stack_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_stack_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_stack_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_stack_outputs")
+
+    def tail_step_count(self) -> int:
+        """control steps that ran with the task epilogue at the control-step kernel's tail (HIP library only)"""
+        if self.lib.tail_step_count is None:
+            raise NativeError(f"{self.lib.path} has no tail_step_count (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        return int(self.lib.tail_step_count(self.h))
 
     def task_pick_outputs(self, task: "PickTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
         self._check(self.lib.task_pick_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_pick_outputs")

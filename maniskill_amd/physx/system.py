@@ -341,6 +341,14 @@ class MssimSystem:
     def task_push_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
         self._sim.task_push_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
 
+    def task_stack_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
+        """StackCube evaluate / obs / reward in one launch (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_stack_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
+
+    def tail_step_count(self) -> int:
+        """control steps so far that ran as one launch with the task epilogue at the kernel's tail (HIP library only)"""
+        return self._sim.tail_step_count()
+
     def task_pick_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
         self._sim.task_pick_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
 
