@@ -40,6 +40,37 @@ typedef struct mssim_stack_task {
 
 int mssim_task_stack_outputs(mssim_handle h, const mssim_stack_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
 
+/* PushT-style evaluate + state observation + dense reward in one launch (envs/tasks/tabletop/push_t.py): the
+ * reference's 64 x 64 pseudo-render of the T block in the goal T's frame, intersected with the goal's template.
+ * obs [N][2*n_dof+17] f32 (qpos, qvel, tcp_pose7, goal_pos3, obj_pose7), reward [N] f32, flags [N][1] u8 = success,
+ * intersection: optional device [N] f32, the count of template pixels hit (success = count / area >= threshold).
+ * `consts` is a device block of MSSIM_PUSHT_CONSTS_WORDS 32-bit words that the env builds once from its own tensors:
+ *   [0, 9)     world_to_goal, 3 x 3 f32 row-major (the inverse of the goal's planar transform, as the env computed it)
+ *   [9, 73)    u of grid column j (f32), [73, 137) v of grid row i (f32): the uv grid's pixel centres
+ *   [137, 265) the template, 64 x 64 bits, bit (64 i + j) = word (64 i + j) / 32, bit (64 i + j) % 32
+ *   [265]      the template's pixel count (int32)
+ * The struct is no larger than mssim_peg_task (the control-step kernel carries every task struct in one union). */
+#define MSSIM_PUSHT_W2G 0
+#define MSSIM_PUSHT_U 9
+#define MSSIM_PUSHT_V 73
+#define MSSIM_PUSHT_TEMPLATE 137
+#define MSSIM_PUSHT_AREA 265
+#define MSSIM_PUSHT_CONSTS_WORDS 266
+typedef struct mssim_pusht_task {
+  int32_t tcp_row, tee_row, goal_row; /* rigid_body_data body rows */
+  float goal_z_rot;           /* 5 pi / 3: reward term cos(yaw - goal_z_rot), yaw = 2 acos(sign(q_z) q_w)              */
+  float intersection_thresh;  /* 0.9 */
+  float reward_div;           /* 1 (dense) or 3 (normalized_dense) */
+  const int32_t* consts;      /* device block, see above */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;     /* optional device [N]: new elapsed_steps >= time_limit */
+  int32_t time_limit;
+  uint8_t* terminated_out;    /* optional device [N]: a copy of success */
+} mssim_pusht_task;
+
+int mssim_task_pusht_outputs(mssim_handle h, const mssim_pusht_task* task, float* obs, float* reward, uint8_t* flags, float* intersection, void* stream);
+
 /* How many control steps of this handle so far ran as one launch with a task epilogue at the control-step kernel's
  * tail (a deferred step_action + fetch consumed by a task_*_outputs call), against the separate epilogue launch.
  * A host counter: no sync. */

@@ -1,2 +1,2 @@
-from .panda import Panda, PandaWristCam
+from .panda import Panda, PandaStick, PandaWristCam
 from .fetch import Fetch

@@ -1,2 +1,3 @@
 from .panda import Panda
+from .panda_stick import PandaStick
 from .panda_wristcam import PandaWristCam

@@ -30,6 +30,7 @@
 // the control-step kernel carries the task structs in one union (DevState::tail_task): a new one must not widen it,
 // or the kernel arguments of every instance change
 static_assert(sizeof(mssim_stack_task) <= sizeof(mssim_peg_task) && alignof(mssim_stack_task) <= alignof(mssim_peg_task), "tail_task union would grow");
+static_assert(sizeof(mssim_pusht_task) <= sizeof(mssim_peg_task) && alignof(mssim_pusht_task) <= alignof(mssim_peg_task), "tail_task union would grow");
 
 #define MAXC 52  // solver blocks per env: contact points + torsional blocks (overflow is reported, never silent); 4 envs x the LDS tables = 40.0 KB per block, 4 blocks per CU
 
@@ -86,9 +87,9 @@ struct DevState {
   // copy-out + task epilogue at the tail of the fused launch (whole control step = one launch); 0 = none
   unsigned tail_fetch;                          // mssim_fetch mask
   mssim_buffers tail_buf;
-  union { mssim_pick_task pick; mssim_push_task push; mssim_peg_task peg; mssim_stack_task stack; } tail_task;  // kind = template TASK
+  union { mssim_pick_task pick; mssim_push_task push; mssim_peg_task peg; mssim_stack_task stack; mssim_pusht_task pusht; } tail_task;  // kind = template TASK
   const int* tail_pairs; int tail_npairs;       // finger <-> object candidate pairs
-  float *tail_obs, *tail_reward, *tail_head;
+  float *tail_obs, *tail_reward, *tail_head;  // tail_head: PegInsertionSide's head_at_hole, PushT's intersection
   uint8_t* tail_flags;
 };
 
@@ -809,6 +810,118 @@ __global__ __launch_bounds__(256) void k_task_stack(DevModel M, DevState S, mssi
   task_stack_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
 }
 
+// PushT pseudo-render (push_t.py pseudo_render_intersection): every template pixel (i, j) of the block's T, at its uv
+// grid centre (U[j], V[i], 1), is mapped by world_to_goal @ tee_to_world, divided by the third row, scaled to pixel
+// indices and truncated toward zero (.long()); an index outside [0, 64) sends the pixel to (0, 0). Index pair (x, y)
+// lands on image row 63 - y, column x (the reference's permute + flip), so (0, 0) lands on row 63, column 0, which the
+// template does not cover. The result counts the template pixels hit by at least one mapped pixel.
+// Runs on the 16 lanes c = 0..15 of one env (all of them call it): each lane maps the template words c, c + 16, ...
+// and sets bits of the env's 128-word bitmap `bm` in LDS; then AND with the template, popcount, and a sum over the
+// 16 lanes. Every lane returns the count.
+MS_DEV void pusht_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+MS_DEV int pusht_intersection16(const int32_t* __restrict__ K, float px, float py, float yaw, int c, unsigned* bm) {
+  for (int w = c; w < 128; w += 16) bm[w] = 0u;
+  pusht_wave_sync();
+  // tee_to_goal = world_to_goal @ [[cos, -sin, px], [sin, cos, py], [0, 0, 1]] (quat_to_zrot + the translation)
+  const float ca = cosf(yaw), sa = sinf(yaw);
+  float W[9], T[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) W[k] = __int_as_float(K[MSSIM_PUSHT_W2G + k]);
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    T[3 * r + 0] = W[3 * r + 0] * ca + W[3 * r + 1] * sa;
+    T[3 * r + 1] = W[3 * r + 0] * -sa + W[3 * r + 1] * ca;
+    T[3 * r + 2] = W[3 * r + 0] * px + W[3 * r + 1] * py + W[3 * r + 2];
+  }
+  const float scale = (float)(64.0 / 2.0 / 0.15);  // (res / 2) / uv_half_width: a double, cast to f32 by the torch op
+  for (int w = c; w < 128; w += 16) {
+    unsigned bits = (unsigned)K[MSSIM_PUSHT_TEMPLATE + w];
+    while (bits) {
+      const int p = 32 * w + (__ffs(bits) - 1);
+      bits &= bits - 1u;
+      const float u = __int_as_float(K[MSSIM_PUSHT_U + (p & 63)]), v = __int_as_float(K[MSSIM_PUSHT_V + (p >> 6)]);
+      const float hx = T[0] * u + T[1] * v + T[2], hy = T[3] * u + T[4] * v + T[5], hw = T[6] * u + T[7] * v + T[8];
+      const float fx = truncf(__fdiv_rn(hx, hw) * scale + 32.f), fy = truncf(__fdiv_rn(hy, hw) * scale + 32.f);
+      const bool ok = fx >= 0.f && fx < 64.f && fy >= 0.f && fy < 64.f;  // (false for NaN as well)
+      const int x = ok ? (int)fx : 0, y = ok ? (int)fy : 0;
+      const int bit = 64 * (63 - y) + x;
+      atomicOr(bm + (bit >> 5), 1u << (bit & 31));
+    }
+  }
+  pusht_wave_sync();
+  int cnt = 0;
+  for (int w = c; w < 128; w += 16) cnt += __popc(bm[w] & (unsigned)K[MSSIM_PUSHT_TEMPLATE + w]);
+  cnt += __shfl_xor(cnt, 8, 16);
+  cnt += __shfl_xor(cnt, 4, 16);
+  cnt += __shfl_xor(cnt, 2, 16);
+  cnt += __shfl_xor(cnt, 1, 16);
+  return cnt;
+}
+
+// PushT evaluate / obs / reward (push_t.py evaluate, _get_obs_extra, compute_dense_reward) on the env's 16 lanes: the
+// intersection over all of them, the rest on lane 0. `bm`: the env's 128 words of LDS.
+MS_DEV void task_pusht_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_pusht_task& T, float* __restrict__ obs,
+                           float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ inter_out, int e, int c, unsigned* bm) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  const float* tee = rowp(T.tee_row);
+  const float tx = tee[0], ty = tee[1], tz = tee[2], qw = tee[3], qz = tee[6];
+  // quat_to_z_euler: 2 acos(sign(q_z) q_w), sign(0) = +1
+  const float yaw = 2.f * acosf(qz < 0.f ? -qw : qw);
+  const int cnt = pusht_intersection16(T.consts, tx, ty, yaw, c, bm);
+  if (c != 0) return;
+  const float frac = __fdiv_rn((float)cnt, (float)T.consts[MSSIM_PUSHT_AREA]);
+  const bool success = frac >= T.intersection_thresh;
+  float* o = obs + (size_t)e * (2 * n + 17);
+  for (int j = 0; j < n; j++) {
+    o[j] = B.art_qpos[(size_t)e * n + j];
+    o[n + j] = B.art_qvel[(size_t)e * n + j];
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* gl = rowp(T.goal_row);
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  for (int i = 0; i < 3; i++) o[k++] = gl[i];
+  for (int i = 0; i < 7; i++) o[k++] = tee[i];
+  // dense reward: rotation, planar distance to the goal, tcp near the block
+  const float rot = (cosf(yaw - T.goal_z_rot) + 1.f) / 2.f;
+  float r = rot * rot / 2.f;
+  const float dx = tx - gl[0], dy = ty - gl[1];
+  const float dg = 1.f - tanhf(5.f * __fsqrt_rn(dx * dx + dy * dy));
+  r += dg * dg / 2.f;
+  const f3 d3 = f3{tx - tcp[0], ty - tcp[1], tz - tcp[2]};
+  r += __fsqrt_rn(1.f - tanhf(5.f * __fsqrt_rn(dot(d3, d3)))) / 20.f;
+  if (success) r = 3.f;
+  reward[e] = __fdiv_rn(r, T.reward_div);
+  flags[e] = success;
+  if (inter_out) inter_out[e] = (float)cnt;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// 16 lanes per env, 16 envs per block of 256 threads, 512 B of LDS per env. FETCH: the launch first performs
+// mssim_fetch(what) for its envs, the rows of an env strided over its 16 lanes (all in one wave).
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_pusht(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_pusht_task T, float* __restrict__ obs,
+                                                     float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ inter_out) {
+  __shared__ unsigned bm[16 * 128];
+  const int c = threadIdx.x & 15, le = threadIdx.x >> 4;
+  const int e = xcd_chunk(blockIdx.x, gridDim.x) * 16 + le;
+  if (e >= S.N) return;  // (whole 16-lane groups)
+  if (FETCH) {
+    const int R = M.n_link + M.n_free + M.n_kin;
+    for (int row = c; row < R; row += 16) fetch_row(M, S, B, what, e, row);
+    for (int j = c; j < M.n_dof; j += 16) fetch_art_joint(M, S, B, what, e, j);
+    __threadfence_block();
+    pusht_wave_sync();
+  }
+  task_pusht_env(M, S, B, T, obs, reward, flags, inter_out, e, c, bm + 128 * le);
+}
+
 // geometric Jacobian of link `link` in the root frame: out [N][6][n_dof] (see include/mssim.h)
 __global__ void k_link_jacobian(DevModel M, DevState S, int link, float* __restrict__ out) {
   const int N = S.N;
@@ -1393,7 +1506,8 @@ int mssim_step(mssim_handle h, int32_t n_substeps, void* stream) {
 }
 
 // TASK: 0 = plain control step, 1 / 2 / 3 = copy-out + PickCube / PushCube / PegInsertionSide epilogue at its tail (one row per
-// env), 4 = copy-out + StackCube epilogue (two rows per env: the Panda with two cubes)
+// env), 4 = copy-out + StackCube epilogue (two rows per env: the Panda with two cubes), 5 = copy-out + PushT epilogue (one row:
+// the 7-joint panda_stick and the T block, 13 velocity components)
 extern "C++" {
 template <int TASK>
 static void launch_control_step(mssim_handle h, const DevState& S, int n_substeps, hipStream_t st) {
@@ -1401,8 +1515,9 @@ static void launch_control_step(mssim_handle h, const DevState& S, int n_substep
   const dim3 block(64 * S16_WAVES);
 #ifdef MSSIM_ONLY_PANDA
   // (timing experiments, scripts/ab_variants.sh: only the benchmark's instances are compiled -- a fifth of the build time)
-  // (TASK 4 is not among them: control_step_with_task leaves StackCube to the separate epilogue launch in this build)
-  hipLaunchKernelGGL((k_solve16<9, TASK == 4 ? 0 : TASK>), env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK), block, 0, st, h->M, S, n_substeps);
+  // (TASK 4 and 5 are not among them: control_step_with_task leaves StackCube and PushT to the separate epilogue launch in
+  // this build)
+  hipLaunchKernelGGL((k_solve16<9, (TASK == 4 || TASK == 5) ? 0 : TASK>), env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK), block, 0, st, h->M, S, n_substeps);
 #else
   if (h->rows_per_env == 4) {  // three to six free bodies: four 16-lane rows (a whole wave) per env, 4 envs per block; the generic-topology instances
     const dim3 grid4 = env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK / 4);
@@ -1431,7 +1546,11 @@ static void launch_control_step(mssim_handle h, const DevState& S, int n_substep
     if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
     else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
     else hipLaunchKernelGGL((k_solve16<0, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
-  } else if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, TASK == 4 ? 0 : TASK>), grid, block, 0, st, h->M, S, n_substeps);
+  } else if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, (TASK == 4 || TASK == 5) ? 0 : TASK>), grid, block, 0, st, h->M, S, n_substeps);
+  else if (h->M.n_dof == 7) {  // (panda_stick; the plain instance keeps the physics of fused and unfused runs the same)
+    if (TASK == 5) hipLaunchKernelGGL((k_solve16<7, 5>), grid, block, 0, st, h->M, S, n_substeps);
+    else hipLaunchKernelGGL((k_solve16<7, 0>), grid, block, 0, st, h->M, S, n_substeps);
+  }
   else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0>), grid, block, 0, st, h->M, S, n_substeps);  // (the Fetch)
   else hipLaunchKernelGGL((k_solve16<0, 0>), grid, block, 0, st, h->M, S, n_substeps);
 #endif
@@ -1593,10 +1712,11 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
 extern "C++" {
 template <int TASK>
 static bool control_step_with_task(mssim_handle h, DevState& S, hipStream_t st) {
-  if (!(h->deferred_action && h->deferred_fetch && h->M.n_dof == 9 && h->deferred_nsub > 0 && st == h->deferred_stream && h->ee.link < 0) || h->has_tri) return false;
+  const int ndof = TASK == 5 ? 7 : 9;  // the joints the task's tail is compiled for (PushT: panda_stick)
+  if (!(h->deferred_action && h->deferred_fetch && h->M.n_dof == ndof && h->deferred_nsub > 0 && st == h->deferred_stream && h->ee.link < 0) || h->has_tri) return false;
   const int rows = TASK == 4 ? 2 : 1;  // the rows per env the task's tail is compiled for
 #ifdef MSSIM_ONLY_PANDA
-  if (rows != 1) return false;  // (only the one-row instances are compiled)
+  if (rows != 1 || TASK == 5) return false;  // (only the Panda's one-row instances are compiled)
 #endif
   if (h->rows_per_env != rows) return false;
   // The tail runs at the kernel's one wave per SIMD: worth it while all blocks are resident at once (4 per CU) and
@@ -1661,6 +1781,28 @@ int mssim_task_stack_outputs(mssim_handle h, const mssim_stack_task* task, float
     hipLaunchKernelGGL(k_task_stack<true>, env_grid(h->N, 64), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
   else
     hipLaunchKernelGGL(k_task_stack<false>, env_grid(h->N, 64), dim3(64), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int mssim_task_pusht_outputs(mssim_handle h, const mssim_pusht_task* task, float* obs, float* reward, uint8_t* flags, float* intersection, void* stream) {
+  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
+  const int rows[3] = {task->tcp_row, task->tee_row, task->goal_row};
+  for (int r : rows)
+    if (r < 0 || r >= R) { h->err = "task_pusht_outputs: body row out of range"; return 1; }
+  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
+  if (!task->consts || !(task->reward_div > 0.f)) { h->err = "task_pusht_outputs: needs the constants block and a reward divisor > 0"; return 3; }
+  {
+    DevState S = h->S;
+    S.tail_task.pusht = *task; S.tail_pairs = nullptr; S.tail_npairs = 0;
+    S.tail_obs = obs; S.tail_reward = reward; S.tail_flags = flags; S.tail_head = intersection;
+    if (control_step_with_task<5>(h, S, (hipStream_t)stream)) { HIPCHK(h, hipGetLastError()); return 0; }
+  }
+  if (h->deferred_action) { const unsigned w = take_deferred_fetch(h); flush_deferred(h, (hipStream_t)stream); h->deferred_fetch = w; }
+  // 16 lanes per env: 16 envs per block of 256
+  const unsigned what = take_deferred_fetch(h);
+  if (what) hipLaunchKernelGGL(k_task_pusht<true>, env_grid(h->N, 16), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, obs, reward, flags, intersection);
+  else hipLaunchKernelGGL(k_task_pusht<false>, env_grid(h->N, 16), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, obs, reward, flags, intersection);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

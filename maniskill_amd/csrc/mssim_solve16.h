@@ -748,8 +748,8 @@ struct SupCoop16 {
 // NDOF > 0: the number of joints is a compile-time constant (9 for the Panda), so the loops over the
 // joints are unrolled and their masks folded; NDOF = 0 reads it from the model.
 // TASK > 0 (with FUSED): the launch ends with the copy-out (mssim_fetch) of its envs and the evaluate / obs /
-// reward epilogue of a task -- 1 PickCube, 2 PushCube, 3 PegInsertionSide (one row per env), 4 StackCube (two rows) -- so
-// that a whole control step (action map, substeps, copy-out, epilogue) is one launch.
+// reward epilogue of a task -- 1 PickCube, 2 PushCube, 3 PegInsertionSide, 5 PushT (one row per env), 4 StackCube (two rows)
+// -- so that a whole control step (action map, substeps, copy-out, epilogue) is one launch.
 // TRI: the model has triangle-mesh shapes (MSSIM_SHAPE_TRIMESH): the narrowphase carries the mesh stage (BVH traversal, one
 // multi-point manifold per triangle in range); instantiated without a task tail only.
 template <int NDOF = 0, int TASK = 0, bool TRI = false, int NR = 1>
@@ -3179,6 +3179,12 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
       if (TASK == 2) task_push_env(M, S, S.tail_buf, S.tail_task.push, S.tail_obs, S.tail_reward, S.tail_flags, e);
       if (TASK == 3) task_peg_env(M, S, S.tail_buf, S.tail_task.peg, S.tail_pairs, S.tail_npairs, S.tail_obs, S.tail_reward, S.tail_flags, S.tail_head, e);
       if (TASK == 4) task_stack_env(M, S, S.tail_buf, S.tail_task.stack, S.tail_pairs, S.tail_npairs, S.tail_obs, S.tail_reward, S.tail_flags, e);
+    }
+    if constexpr (TASK == 5) {
+      // PushT: the pseudo-render on the env's 16 lanes, its bitmap in the env's own LDS region (free after the last
+      // substep); `live` is uniform over the env's lanes
+      static_assert(NR == 1 && S16_ENV_FLOATS >= 128, "PushT's tail: one row, 128 words of LDS per env");
+      if (live) task_pusht_env(M, S, S.tail_buf, S.tail_task.pusht, S.tail_obs, S.tail_reward, S.tail_flags, S.tail_head, e, c, reinterpret_cast<unsigned*>(L));
     }
     PH(8);
   }

@@ -1,2 +1,2 @@
-from .tabletop import PegInsertionSideEnv, PickCubeEnv, PushCubeEnv, StackCubeEnv
+from .tabletop import PegInsertionSideEnv, PickCubeEnv, PushCubeEnv, PushTEnv, StackCubeEnv
 from .empty_env import EmptyEnv

@@ -310,6 +310,16 @@ class SceneModelBuilder:
                     body_items.setdefault(b, []).append(
                         geom.transform_inertial(link_rel[lname], link.mass, link.com, link.inertia)
                     )
+                elif not link.has_inertial:
+                    # no <inertial>: SAPIEN's loaders take mass and inertia from the collision shapes at their density
+                    # (1000 kg/m^3 unless configured; the reference restates it in _mjcf_loader.py). Not pinned against
+                    # SAPIEN itself
+                    for s in art.link_shapes.get(lname, []):
+                        ms, cs, Is = s.mass_properties()
+                        if ms > 0:
+                            body_items.setdefault(b, []).append(
+                                geom.transform_inertial(geom.compose(link_rel[lname], s.pose), ms, cs, Is)
+                            )
                 # fixed links inherit the gravity flag of ... each link separately in the
                 # reference; a folded body uses the flag of its joint-bearing link.
                 for s in art.link_shapes.get(lname, []):

@@ -160,6 +160,13 @@ class StackTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class PushTTask(C.Structure):
+    """mssim_pusht_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("tee_row", C.c_int32), ("goal_row", C.c_int32),
+                ("goal_z_rot", C.c_float), ("intersection_thresh", C.c_float), ("reward_div", C.c_float), ("consts", C.c_void_p),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -219,6 +226,7 @@ class NativeLib:
         H = C.c_void_p
         for name, restype, argtypes in (
             ("task_stack_outputs", C.c_int, [H, C.POINTER(StackTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_pusht_outputs", C.c_int, [H, C.POINTER(PushTTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
         ):
             if hasattr(self.lib, self.prefix + name):
@@ -374,6 +382,11 @@ class NativeSim:
         if self.lib.task_stack_outputs is None:
             raise NativeError(f"{self.lib.path} has no task_stack_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.task_stack_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_stack_outputs")
+
+    def task_pusht_outputs(self, task: "PushTTask", obs_ptr, reward_ptr, flags_ptr, intersection_ptr=None, stream=None):
+        if self.lib.task_pusht_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_pusht_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_pusht_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, intersection_ptr, stream), "task_pusht_outputs")
 
     def tail_step_count(self) -> int:
         """control steps that ran with the task epilogue at the control-step kernel's tail (HIP library only)"""

@@ -345,6 +345,12 @@ class MssimSystem:
         """StackCube evaluate / obs / reward in one launch (include/mssim_hip_tasks.h; HIP library only)"""
         self._sim.task_stack_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
 
+    def task_pusht_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor, intersection: torch.Tensor = None):
+        """PushT evaluate / obs / reward in one launch; `intersection` [N] f32 (optional): template pixels hit
+        (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_pusht_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(),
+                                     None if intersection is None else intersection.data_ptr(), self._stream())
+
     def tail_step_count(self) -> int:
         """control steps so far that ran as one launch with the task epilogue at the kernel's tail (HIP library only)"""
         return self._sim.tail_step_count()

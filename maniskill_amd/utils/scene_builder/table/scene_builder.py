@@ -47,11 +47,14 @@ class TableSceneBuilder(SceneBuilder):
             qpos = np.array([0.0, -np.pi / 8, 0, -np.pi * 5 / 8, 0, np.pi * 3 / 4, np.pi / 4, 0.04, 0.04])
         elif uid == "panda_wristcam":
             qpos = np.array([0.0, np.pi / 8, 0, -np.pi * 5 / 8, 0, np.pi * 3 / 4, -np.pi / 4, 0.04, 0.04])
+        elif uid == "panda_stick":  # (no fingers: no gripper overwrite below)
+            qpos = np.array([0.0, np.pi / 8, 0, -np.pi * 5 / 8, 0, np.pi * 3 / 4, np.pi / 4])
         elif uid in (None, "none"):
             return
         else:
             raise NotImplementedError(f"table scene initialisation for robot {uid!r} is not part of this build")
         qpos = self._noisy_qpos(env_idx, qpos)
-        qpos[:, -2:] = 0.04
+        if uid != "panda_stick":
+            qpos[:, -2:] = 0.04
         self.env.agent.reset(qpos)
         self.env.agent.robot.set_pose(cache["root"])
