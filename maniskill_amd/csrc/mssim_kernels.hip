@@ -622,7 +622,9 @@ MS_DEV void task_push_env(const DevModel& M, const DevState& S, const mssim_buff
   // evaluate (push_cube.py:165-176) and dense reward (:209-232)
   const float dx = ob[0] - gl[0], dy = ob[1] - gl[1];
   const float obj_to_goal = sqrtf(dx * dx + dy * dy);
-  const bool success = obj_to_goal < T.goal_radius && ob[2] < T.cube_half_size + 5e-3f;
+  // the lift threshold as the torch path forms it: half + 5e-3 in double, rounded once (0.02f + 5e-3f is one ulp below
+  // float(0.025), and a cube at exactly that height was judged differently; tests/task_cases.py exact edges)
+  const bool success = obj_to_goal < T.goal_radius && ob[2] < (float)((double)T.cube_half_size + 5e-3);
   const f3 push_p = f3{ob[0] - T.cube_half_size - 0.005f, ob[1], ob[2]};
   const float dist = norm(push_p - f3{tcp[0], tcp[1], tcp[2]});
   float r = 1.f - tanhf(5.f * dist);
@@ -895,7 +897,9 @@ MS_DEV void task_pusht_env(const DevModel& M, const DevState& S, const mssim_buf
   const float dg = 1.f - tanhf(5.f * __fsqrt_rn(dx * dx + dy * dy));
   r += dg * dg / 2.f;
   const f3 d3 = f3{tx - tcp[0], ty - tcp[1], tz - tcp[2]};
-  r += __fsqrt_rn(1.f - tanhf(5.f * __fsqrt_rn(dot(d3, d3)))) / 20.f;
+  // 1 - tanh x as 2 / (e^2x + 1): far from the block 1 - tanhf cancels to a few ulp of 1, which the square root
+  // magnifies 100-fold (7.6e-7 against float64 at 1.2 m, tests/test_gpu_task_epilogues.py); x >= 0, e^2x = inf gives 0
+  r += __fsqrt_rn(__fdiv_rn(2.f, expf(10.f * __fsqrt_rn(dot(d3, d3))) + 1.f)) / 20.f;
   if (success) r = 3.f;
   reward[e] = __fdiv_rn(r, T.reward_div);
   flags[e] = success;

@@ -159,8 +159,9 @@ class ActorBuilder:
         comp = self.build_physx_component()
         comp.name = self.name
         init = Pose.create(self.initial_pose if self.initial_pose is not None else Pose.create_from_pq(), device=self.scene.device)
-        if self.scene_idxs is not None and len(self.scene_idxs) != self.scene.num_envs:
-            # fragment: lives in a subset of envs until merged
+        if self.scene_idxs is not None and (len(self.scene_idxs) != self.scene.num_envs or self.scene.num_envs == 1):
+            # fragment: lives in a subset of envs until merged (with one env the "subset" is that env: still a fragment, so
+            # that tasks which build one actor per env and merge them work at num_envs = 1)
             frag = Actor(self.scene, self.name, self.physx_body_type, init, has_collision_shapes=len(self.collision_shapes) > 0)
             frag._fragment = dict(scene_idxs=list(self.scene_idxs), shapes=self.shapes, linear_damping=self.linear_damping,
                                   angular_damping=self.angular_damping)
