@@ -394,6 +394,8 @@ int MSSIM_FN(overflow_count)(mssim_handle h, void* stream);
  *   flags[j] & 16 / & 32: a is multiplied by cos / sin of qpos[(flags[j] >> 8) & 31] -- the forward velocity of a planar
  *   base whose x, y and yaw are joints of the articulation, given in the base's own frame
  *   (agents/controllers/pd_base_vel.py:43-70: x joint: 16, y joint: 32, both on the forward column, yaw index in bits 8..12)
+ *   non-finite actions follow torch.clip: a NaN stays a NaN (it reaches the target of the dofs that read its column, and
+ *   every dof of the end-effector block), +-inf clips to the bound of a row flagged 2 and is handed on by any other row
  * writes both the user-visible target_qpos buffer and the simulation state. All arrays [n_dof], host.
  * apply_action / step_action / defer_step_action fail (non-zero, last_error) when `action_dim` does not cover every
  * mapped column (the reference asserts action.shape == (num_envs, action_dim), base_controller.py:120-133). */

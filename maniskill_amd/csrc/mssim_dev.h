@@ -23,6 +23,8 @@ MS_DEV f3 cross(f3 a, f3 b) { return f3{a.y * b.z - a.z * b.y, a.z * b.x - a.x *
 // -fno-hip-fp32-correctly-rounded-divide-sqrt; none of the quantities here is denormal or needs the last ulp
 MS_DEV float rcp_f(float x) { return __builtin_amdgcn_rcpf(x); }  // callers keep |x| out of the denormal range (there the result is +-inf)
 MS_DEV float rcp_safe(float x) { return __builtin_amdgcn_rcpf(fabsf(x) > 1e-30f ? x : copysignf(1e-30f, x)); }  // finite for any finite x
+// clip to [-1, 1] as torch.clip / numpy.clip do: a NaN stays a NaN (fminf / fmaxf would return the bound instead)
+MS_DEV float clip_unit(float a) { return a < -1.f ? -1.f : (a > 1.f ? 1.f : a); }
 MS_DEV float sqrt_f(float x) { return __builtin_amdgcn_sqrtf(x); }
 MS_DEV float rsq_f(float x) { return __builtin_amdgcn_rsqf(x); }
 MS_DEV float norm(f3 a) { return sqrt_f(dot(a, a)); }

@@ -406,7 +406,7 @@ __global__ void k_apply_action(DevModel M, DevState S, mssim_buffers B, const fl
     if (cj < 0) continue;
     float a = action[(size_t)e * adim + cj];
     if (flags[j] & 2) {
-      a = fminf(fmaxf(a, -1.f), 1.f);
+      a = clip_unit(a);
       a = 0.5f * (hi[j] + lo[j]) + 0.5f * (hi[j] - lo[j]) * a;
     }
     if (flags[j] & 48) {  // forward velocity of a planar base in its own frame (include/mssim.h set_action_map)
@@ -435,7 +435,7 @@ __global__ void k_apply_action(DevModel M, DevState S, mssim_buffers B, const fl
     for (int r = 0; r < 3; r++) {
       float a = action[(size_t)e * adim + ee.col0 + r];
       if (ee.flags & 2) {
-        a = fminf(fmaxf(a, -1.f), 1.f);
+        a = clip_unit(a);
         a = 0.5f * (ee.hi + ee.lo) + 0.5f * (ee.hi - ee.lo) * a;
       }
       av[r] = a;

@@ -829,7 +829,7 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
       float a = S.act[(size_t)e * S.act_dim + cj];
       const int fl = S.act_flags[c];
       if (fl & 2) {
-        a = fminf(fmaxf(a, -1.f), 1.f);
+        a = clip_unit(a);
         a = 0.5f * (S.act_hi[c] + S.act_lo[c]) + 0.5f * (S.act_hi[c] - S.act_lo[c]) * a;
       }
       if (fl & 48) {  // forward velocity of a planar base, given in its own frame: x / y joint get its cos / sin share

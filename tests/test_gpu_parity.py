@@ -270,7 +270,16 @@ def test_link_jacobian_matches_oracle():
     N = 128
     gpu, cpu = make_pair(model, N)
     q, qd, tq, cube = random_tabletop_state(N, 7, spread=1.0)
+    # tilted, displaced roots (env 0 keeps the builder's): the Jacobian is expressed in the root frame
+    g = torch.Generator().manual_seed(7)
+    rq = torch.randn(N, 4, generator=g)
+    rq = rq / rq.norm(dim=1, keepdim=True)
+    rq[0] = torch.tensor([1.0, 0, 0, 0])
+    rp = 2 * torch.rand(N, 3, generator=g) - 1
+    rp[0] = 0
     for px in (gpu, cpu):
+        px.cuda_rigid_body_data.torch()[:N, :3] += rp.to(px.device)
+        px.cuda_rigid_body_data.torch()[:N, 3:7] = rq.to(px.device)
         set_state(px, model, N, q, qd, tq, cube)
         px.gpu_update_articulation_kinematics()
     for name in ("panda_hand_tcp", "panda_link3", "panda_rightfinger"):

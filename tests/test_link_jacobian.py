@@ -31,8 +31,24 @@ def test_link_jacobian_matches_finite_differences():
     g = torch.Generator().manual_seed(5)
     lo = torch.tensor(model.arrays["dof_limit"][:, 0]), torch.tensor(model.arrays["dof_limit"][:, 1])
     q0 = (lo[0] + (lo[1] - lo[0]) * torch.rand(N, model.n_dof, generator=g)).float()
-    # a tilted, displaced base so that the root-frame convention is exercised
-    root = px.cuda_articulation_root_pose.torch() if hasattr(px, "cuda_articulation_root_pose") else None
+    # a tilted, displaced base (row 0 of the body table) so that the root-frame convention is exercised: the finite
+    # differences below are of WORLD poses and are rotated into the root frame before they are compared; env 0 keeps
+    # the builder's pose
+    rq = torch.randn(N, 4, generator=g, dtype=torch.float64)
+    rq = rq / rq.norm(dim=1, keepdim=True)
+    rq[0] = torch.tensor([1.0, 0, 0, 0], dtype=torch.float64)
+    rq = rq.float().double()
+    rq = rq / rq.norm(dim=1, keepdim=True)
+    rp = 2 * torch.rand(N, 3, generator=g) - 1
+    px.cuda_rigid_body_data.torch()[:N, :3] += rp * torch.tensor([[0.0]] + [[1.0]] * (N - 1))
+    px.cuda_rigid_body_data.torch()[:N, 3:7] = rq.float()
+    assert float(rq[1:, 0].abs().max()) < 0.999
+    conj = torch.tensor([1.0, -1, -1, -1], dtype=torch.float64)
+
+    def to_root(v):
+        """world vector -> root frame: q* (0, v) q"""
+        return _quat_mul(_quat_mul(rq * conj, torch.cat([torch.zeros(N, 1, dtype=torch.float64), v], 1)), rq)[:, 1:]
+
     eps = 1e-3  # buffers are f32: a larger step keeps the difference quotient above the rounding noise
     for link in (model.link_names.index("panda_hand_tcp"), model.link_names.index("panda_link4"), model.link_names.index("panda_leftfinger")):
         px.cuda_articulation_qpos.torch()[:] = q0
@@ -46,9 +62,9 @@ def test_link_jacobian_matches_finite_differences():
             Pp = _link_poses(px, model, N)[link]
             px.cuda_articulation_qpos.torch()[:] = qm
             Pm = _link_poses(px, model, N)[link]
-            lin = (Pp[:, :3] - Pm[:, :3]) / (2 * eps)
-            dq = _quat_mul(Pp[:, 3:], Pm[:, 3:] * torch.tensor([1.0, -1, -1, -1], dtype=torch.float64))
-            ang = 2 * dq[:, 1:] / (2 * eps) * torch.sign(dq[:, :1])
+            lin = to_root((Pp[:, :3] - Pm[:, :3]) / (2 * eps))
+            dq = _quat_mul(Pp[:, 3:], Pm[:, 3:] * conj)
+            ang = to_root(2 * dq[:, 1:] / (2 * eps) * torch.sign(dq[:, :1]))
             assert torch.allclose(J[:, :3, j], lin, atol=2e-4), (link, j, (J[:, :3, j] - lin).abs().max())
             assert torch.allclose(J[:, 3:, j], ang, atol=2e-4), (link, j, (J[:, 3:, j] - ang).abs().max())
     # columns of joints that do not move the link are exactly zero (finger joints for link 4)
