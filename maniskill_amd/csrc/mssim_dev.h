@@ -9,7 +9,6 @@
 struct f3 {
   float x, y, z;
 };
-MS_DEV f3 mk3(float x, float y, float z) { return f3{x, y, z}; }
 MS_DEV f3 operator+(f3 a, f3 b) { return f3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 MS_DEV f3 operator-(f3 a, f3 b) { return f3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 MS_DEV f3 operator-(f3 a) { return f3{-a.x, -a.y, -a.z}; }

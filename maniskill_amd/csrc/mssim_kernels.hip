@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -32,7 +33,7 @@
 static_assert(sizeof(mssim_stack_task) <= sizeof(mssim_peg_task) && alignof(mssim_stack_task) <= alignof(mssim_peg_task), "tail_task union would grow");
 static_assert(sizeof(mssim_pusht_task) <= sizeof(mssim_peg_task) && alignof(mssim_pusht_task) <= alignof(mssim_peg_task), "tail_task union would grow");
 
-#define MAXC 52  // solver blocks per env: contact points + torsional blocks (overflow is reported, never silent); 4 envs x the LDS tables = 40.0 KB per block, 4 blocks per CU
+#include "mssim_limits.h"  // MAXC and the other capacities the host shares with the control-step kernel
 
 struct DevModel {
   int n_dof, n_tendon, n_link, n_free, n_kin, n_shape, n_pair;
@@ -62,7 +63,7 @@ struct DevState {
   float *root, *q, *qd, *qt, *qdt, *qf, *qacc;  // [7][N], [n_dof][N] ...
   float *free_s, *free_force, *kin;             // [n_free*13][N], [n_free*3][N], [n_kin*7][N]
   float* free_wake;                             // [n_free][N] seconds of low energy left before the body sleeps; <= 0: asleep
-  float* pcm;                                   // [N][MSSIM_PCM_SLOTS][48] persistent contact manifolds (mssim_solve16.h S16_PCM_LEN)
+  float* pcm;                                   // [N][MSSIM_PCM_SLOTS][48] persistent contact manifolds (mssim_limits.h S16_PCM_LEN)
   int* pcm_tick;                                // [N] substep counter of the cache
   float* warm;                                  // [4 n_pair][N][4] contact multipliers (n, t1, t2) + substep stamp per (pair, manifold slot)
   float* tri_clear;                             // [4 n_mesh_pair][N] per (convex shape, mesh) pair: the shape's bounding-sphere centre in the mesh frame at its last
@@ -119,8 +120,6 @@ struct TopoPanda {  // panda_v2/v3: 7 revolute chain + 2 prismatic fingers on bo
   MS_DEV constexpr bool revolute(int j) const { return j < 7; }
   MS_DEV constexpr unsigned anc(int j) const { return j <= 7 ? ((1u << j) - 1u) : 0x7Fu; }
 };
-static const int kPandaParent[9] = {-1, 0, 1, 2, 3, 4, 5, 6, 6};
-static const int kPandaType[9] = {0, 0, 0, 0, 0, 0, 0, 1, 1};
 
 // spatial helpers (world frame, about the origin O = articulation root position)
 struct sv6 { f3 w, v; };                    // motion
@@ -224,14 +223,6 @@ __global__ __launch_bounds__(64) void k_fk(DevModel M, DevState S) {
 }
 
 // ------------------------------------------------------------------------------------------------
-MS_DEV pose_t body_pose_of(const DevModel& M, const DevState& S, int kind, int index, int e) {
-  const int N = S.N;
-  if (kind == MSSIM_BODY_ART) return index < 0 ? pose_soa(S.root, 0, N, e) : pose_soa(S.bodypose, 7 * index, N, e);
-  if (kind == MSSIM_BODY_FREE) return pose_soa(S.free_s, 13 * index, N, e);
-  if (kind == MSSIM_BODY_KIN) return pose_soa(S.kin, 7 * index, N, e);
-  return pose_t{f3{0, 0, 0}, q4{1, 0, 0, 0}};
-}
-
 // the 10 inertial parameters of free body b in env e (per-env override or shared table)
 MS_DEV void free_inertial_of(const DevModel& M, int N, int b, int e, float* out) {
   const int slot = M.free_env_slot[b];
@@ -966,6 +957,7 @@ __global__ void k_i2f(const int* src, float* dst, size_t count) {
 // =================================================================================================
 // host side
 #include "mssim_solve16.h"
+#include "mssim_model_pack.h"
 
 struct mssim_sim {
   int device = 0;
@@ -1035,6 +1027,14 @@ static int dalloc(mssim_sim* S, size_t count, Tt** dst) {
   *dst = (Tt*)d;
   return 0;
 }
+static int dset(mssim_sim* S, float* dst, int byte, size_t count) {
+  HIPCHK(S, hipMemset(dst, byte, count * sizeof(float)));
+  return 0;
+}
+static int dput(mssim_sim* S, float* dst, const std::vector<float>& v) {
+  HIPCHK(S, hipMemcpy(dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
 
 extern "C" {
 
@@ -1050,339 +1050,85 @@ void mssim_destroy(mssim_handle h) {
   delete h;
 }
 
+// validate -> pack (mssim_model_pack.h: host only, a malformed model is turned down before the device is touched) ->
+// upload -> initialise the state
 int mssim_create(const mssim_model_desc* d, int32_t num_envs, int32_t device, mssim_handle* out) {
-  if (!d || !out || num_envs <= 0) { g_create_error = "bad arguments"; return 1; }
-  if (d->abi_version != MSSIM_ABI_VERSION) { g_create_error = "ABI version mismatch"; return 2; }
-  if (d->n_dof > MSSIM_MAX_DOF || d->n_free > MSSIM_MAX_FREE) { g_create_error = "model exceeds MSSIM_MAX_DOF / MSSIM_MAX_FREE"; return 3; }
-  // the control-step kernel keeps an env on one or two 16-lane rows (one velocity component per lane: the joints in row 0, the free
-  // bodies behind them or, when that is more than 16 components, in a row of their own) and its scene in fixed LDS tables
-  // (rows per env: 1 while joints and free bodies fit 16 lanes together; else the joints in row 0 and two free bodies per further row)
-  const int rows_per_env = d->n_dof + 6 * d->n_free <= S16_LANES ? 1 : (d->n_free <= 2 ? 2 : 4);
-  if (d->n_dof > S16_LANES || d->n_free > S16_MAX_FREE_(4) || d->n_kin > S16_MAX_KIN || d->n_shape > S16_MAX_SHAPE_(rows_per_env) || d->n_pair > 56 * 16) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "model exceeds the control-step kernel's tables: %d joints (max %d), %d free bodies (max %d), %d kinematic bodies (max %d), "
-             "%d shapes (max %d with %d velocity components), %d candidate pairs (max %d)", d->n_dof, S16_LANES, d->n_free, S16_MAX_FREE_(4), d->n_kin, S16_MAX_KIN, d->n_shape,
-             S16_MAX_SHAPE_(rows_per_env), d->n_dof + 6 * d->n_free, d->n_pair, 56 * 16);
-    g_create_error = msg;
-    return 9;
-  }
-  for (int j = 0; j < d->n_dof; j++)
-    if (d->dof_parent[j] >= j) { g_create_error = "dof_parent must be topologically sorted"; return 4; }
-  for (int p = 0; p < d->n_pair; p++)
-    if (d->pair_shape[2 * p] < 0 || d->pair_shape[2 * p] >= d->n_shape || d->pair_shape[2 * p + 1] < 0 || d->pair_shape[2 * p + 1] >= d->n_shape) {
-      g_create_error = "pair_shape names a shape that does not exist";
-      return 4;
-    }
-  for (int s = 0; s < d->n_shape; s++)
-    if (d->shape_type[s] == MSSIM_SHAPE_CONVEX && (d->shape_hull[2 * s + 1] < 4 || d->shape_hull[2 * s + 1] > MSSIM_MAX_HULL_VERTS)) {
-      g_create_error = "convex hull vertex count out of range";
-      return 5;
-    }
-  // tables the kernels index without checks (a malformed model gets an error string here, not an out-of-bounds device read)
-  if (d->n_tri_node >= (1 << 17) || d->n_tri >= (1 << 24)) { g_create_error = "triangle meshes: more than 131071 BVH nodes or 16777215 triangles (the shape word packs the root node into 17 bits)"; return 5; }
-  for (int nd = 0; nd < d->n_tri_node; nd++)
-    for (int c = 0; c < 16; c++) {
-      const float* nb = d->tri_bvh + (size_t)nd * 112;
-      if (!(nb[6 * c] <= nb[6 * c + 3])) continue;  // (min > max: no child)
-      int32_t ref;
-      std::memcpy(&ref, nb + 96 + c, 4);
-      if (ref >= 0 ? ref >= d->n_tri_node : ~ref >= d->n_tri) { g_create_error = "tri_bvh: a child reference points outside the node / triangle tables"; return 5; }
-    }
-  if (d->n_env_shape > 0)
-    for (int s = 0; s < d->n_shape; s++)
-      if (d->shape_env_slot[s] >= d->n_env_shape) { g_create_error = "shape_env_slot names a slot beyond n_env_shape"; return 5; }
-  if (d->n_env_free > 0)
-    for (int b = 0; b < d->n_free; b++)
-      if (d->free_env_slot[b] >= d->n_env_free) { g_create_error = "free_env_slot names a slot beyond n_env_free"; return 5; }
-  for (int s = 0; s < d->n_shape; s++)
-    if (d->shape_type[s] == MSSIM_SHAPE_CONVEX && (d->shape_hull[2 * s] < 0 || d->shape_hull[2 * s] + d->shape_hull[2 * s + 1] > d->n_hull_verts)) {
-      g_create_error = "convex hull: vertex range outside hull_verts";
-      return 5;
-    }
-  mssim_sim* S = new mssim_sim();
+  if (!out) { g_create_error = "bad arguments"; return 1; }
+  PackedModel P;
+  int rc = validate_model(d, num_envs, &g_create_error);
+  if (!rc) rc = pack_model(d, num_envs, &P, &g_create_error);
+  if (rc) return rc;
+  const hipError_t e0 = hipSetDevice(device);
+  if (e0 != hipSuccess) { g_create_error = std::string("hipSetDevice: ") + hipGetErrorString(e0); return 6; }
+  // The handle frees what it holds on every return but the last. The first device call that fails sets rc and its
+  // message; every step after it is skipped, and the one failure exit is at the end.
+  std::unique_ptr<mssim_sim, void (*)(mssim_sim*)> owner(new mssim_sim(), mssim_destroy);
+  mssim_sim* S = owner.get();
+  auto up = [&](const auto* src, size_t count, auto dst) { if (!rc) rc = upload(S, src, count, dst); };   // a model array
+  auto upv = [&](const auto& v, auto dst) { up(v.data(), v.size(), dst); };                               // a packed table
+  auto al = [&](size_t count, auto dst) { if (!rc) rc = dalloc(S, count, dst); };                         // zeroed state
+  auto empty = [&](float* dst, size_t count) { if (!rc) rc = dset(S, dst, 0xFF, count); };                // all bits set: int -1 / NaN
+  auto put = [&](float* dst, size_t at, const std::vector<float>& v) { if (!rc) rc = dput(S, dst + at, v); };
   S->device = device;
   S->N = num_envs;
-  S->rows_per_env = rows_per_env;
-  hipError_t e0 = hipSetDevice(device);
-  if (e0 != hipSuccess) { g_create_error = std::string("hipSetDevice: ") + hipGetErrorString(e0); delete S; return 6; }
+  S->rows_per_env = P.rows_per_env;
+  S->has_tri = P.has_tri;
+  S->panda = P.panda;
   { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) S->n_cu = ncu; }
+  const size_t n = d->n_dof, ns = d->n_shape, nf = d->n_free, np = d->n_pair, N = num_envs;
+  S->h_shape_row.assign(d->shape_row, d->shape_row + ns);
+  S->h_pair_shape.assign(d->pair_shape, d->pair_shape + 2 * np);
+
   DevModel& M = S->M;
   M.n_dof = d->n_dof; M.n_tendon = d->n_tendon; M.n_link = d->n_link; M.n_free = d->n_free; M.n_kin = d->n_kin;
   M.n_shape = d->n_shape; M.n_pair = d->n_pair;
-  const int n = d->n_dof, ns = d->n_shape;
-  std::vector<unsigned> anc(n > 0 ? n : 1, 0u);
-  for (int j = 0; j < n; j++)
-    for (int i = d->dof_parent[j]; i >= 0; i = d->dof_parent[i]) anc[j] |= 1u << i;
-  int rc = 0;
-#define UP(field, count) if ((rc = upload(S, d->field, (size_t)(count), &M.field))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-  UP(dof_parent, n) UP(dof_type, n) UP(body_gravity, n) UP(tendon_dof, 2 * d->n_tendon) UP(link_body, d->n_link) UP(free_gravity, d->n_free)
-  UP(dof_frame, 7 * n) UP(dof_axis, 3 * n) UP(dof_limit, 2 * n) UP(dof_drive, 4 * n) UP(dof_armature, n) UP(body_inertial, 10 * n)
-  UP(tendon_param, 5 * d->n_tendon) UP(link_frame, 7 * d->n_link) UP(free_inertial, 10 * d->n_free) UP(free_damping, 2 * d->n_free)
-  UP(shape_type, ns) UP(shape_row, ns) UP(pair_shape, 2 * d->n_pair)
-  S->h_shape_row.assign(d->shape_row, d->shape_row + ns);
-  S->h_pair_shape.assign(d->pair_shape, d->pair_shape + 2 * (size_t)d->n_pair);
-  UP(shape_frame, 7 * ns) UP(shape_param, 4 * ns) UP(shape_material, 4 * ns) UP(shape_bound, 4 * ns)
-#undef UP
-  // device copy of env_shape_param (row format below)
-  std::vector<float> env_param_dev;
-  {
-    // hull vertices are repacked so that every hull starts on a multiple of 8 vertices and is padded
-    // to a multiple of 8 with copies of its vertex 0: `support()` reads whole 8-vertex batches as six
-    // aligned 16-byte loads, and a copy of vertex 0 can never win its strict first-maximum scan
-    std::vector<float> hv;
-    std::vector<int32_t> sh(2 * (ns > 0 ? ns : 1), 0);
-    std::vector<std::pair<std::pair<int, int>, int>> seen;  // (start, count) -> new start
-    auto repacked = [&](int st, int cnt) {
-      for (auto& kv : seen) if (kv.first.first == st && kv.first.second == cnt) return kv.second;
-      const int found = (int)(hv.size() / 3);
-      for (int i = 0; i < (cnt + 7) / 8 * 8; i++) {
-        const float* v = d->hull_verts + 3 * (size_t)(st + (i < cnt ? i : 0));
-        hv.push_back(v[0]); hv.push_back(v[1]); hv.push_back(v[2]);
-      }
-      seen.push_back({{st, cnt}, found});
-      return found;
-    };
-    for (int s2 = 0; s2 < ns; s2++) {
-      const int st = d->shape_hull[2 * s2], cnt = d->shape_hull[2 * s2 + 1];
-      if (d->shape_type[s2] == MSSIM_SHAPE_TRIMESH) {  // (root node of its BVH, no hull vertices)
-        if (st < 0 || st >= d->n_tri_node || d->shape_body_kind[s2] == MSSIM_BODY_FREE || d->shape_body_kind[s2] == MSSIM_BODY_ART) {
-          g_create_error = "triangle mesh: BVH root out of range, or the mesh belongs to a moving body (fixed / kinematic bodies only)";
-          mssim_destroy(S);
-          return 8;
-        }
-        sh[2 * s2] = st;
-        sh[2 * s2 + 1] = 0;
-        S->has_tri = true;
-        continue;
-      }
-      sh[2 * s2 + 1] = cnt;
-      if (cnt <= 0) continue;
-      sh[2 * s2] = repacked(st, cnt);
-    }
-    if (d->n_env_shape > 0 && d->num_envs == num_envs) {
-      // device rows of every per-env shape: word 0 = type | vertex count << 3 | first vertex << 10 (bit pattern),
-      // rows 1..3 = the three parameters of a primitive, or the half extents of a hull's box for the cull
-      const size_t NE = (size_t)num_envs;
-      env_param_dev.assign(d->env_shape_param, d->env_shape_param + (size_t)4 * d->n_env_shape * NE);
-      for (int s2 = 0; s2 < ns; s2++) {
-        const int slot = d->shape_env_slot[s2];
-        if (slot < 0) continue;
-        for (size_t e = 0; e < NE; e++) {
-          const float* src = d->env_shape_param;
-          const int tcode = (int)src[(size_t)(4 * slot + 3) * NE + e];
-          const int type = tcode > 0 ? tcode - 1 : d->shape_type[s2];
-          // (a triangle mesh only in a slot whose own type is TRIMESH: the mesh variant of the kernel is chosen by the shared types)
-          const bool env_mesh = type == MSSIM_SHAPE_TRIMESH && d->shape_type[s2] == MSSIM_SHAPE_TRIMESH;
-          if ((type < MSSIM_SHAPE_BOX || type > MSSIM_SHAPE_NONE) && !env_mesh) { g_create_error = "per-env shape type out of range (planes cannot be per-env shapes; a triangle mesh only in a slot that is a triangle mesh)"; mssim_destroy(S); return 8; }
-          int32_t word = type;
-          float rows[3] = {src[(size_t)(4 * slot) * NE + e], src[(size_t)(4 * slot + 1) * NE + e], src[(size_t)(4 * slot + 2) * NE + e]};
-          if (type == MSSIM_SHAPE_NONE) rows[0] = rows[1] = rows[2] = 0.f;
-          if (env_mesh) {
-            // this env's mesh: rows = first triangle, triangle count, root node of its BVH. The device row gets the root in
-            // the word's upper bits and the mesh's half extents about its bound centre (shape frame) in the rows.
-            const int first = (int)rows[0], count = (int)rows[1], root = (int)rows[2];
-            if (first < 0 || count < 0 || first + count > d->n_tri || root < 0 || root >= d->n_tri_node) { g_create_error = "per-env triangle mesh: triangle range / root node out of range"; mssim_destroy(S); return 8; }
-            float fr[7], cb[3];
-            for (int k = 0; k < 7; k++) fr[k] = d->env_shape_frame[(size_t)(7 * slot + k) * NE + e];
-            for (int k = 0; k < 3; k++) cb[k] = d->env_shape_bound[(size_t)(4 * slot + k) * NE + e] - fr[k];
-            const float nq = std::sqrt(fr[3] * fr[3] + fr[4] * fr[4] + fr[5] * fr[5] + fr[6] * fr[6]);
-            const float qw = fr[3] / nq, qx = fr[4] / nq, qy = fr[5] / nq, qz = fr[6] / nq;
-            const float R[3][3] = {{1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy)},
-                                   {2 * (qx * qy + qw * qz), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qw * qx)},
-                                   {2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), 1 - 2 * (qx * qx + qy * qy)}};
-            float cs[3];
-            for (int k = 0; k < 3; k++) cs[k] = R[0][k] * cb[0] + R[1][k] * cb[1] + R[2][k] * cb[2];
-            rows[0] = rows[1] = rows[2] = 0.f;
-            for (int t = first; t < first + count; t++) {
-              const float* q = d->tri_soup + 12 * (size_t)t;
-              for (int c3 = 0; c3 < 3; c3++)
-                for (int k = 0; k < 3; k++) rows[k] = std::max(rows[k], std::fabs(q[k] + q[3 + 3 * c3 + k] - cs[k]));
-            }
-            word |= root << 10;
-          }
-          if (type == MSSIM_SHAPE_CONVEX) {
-            const int st = (int)rows[0], cnt = (int)rows[1];
-            if (cnt < 1 || cnt > MSSIM_MAX_HULL_VERTS || st < 0 || st + cnt > d->n_hull_verts) { g_create_error = "per-env hull reference out of range"; mssim_destroy(S); return 8; }
-            const int found = repacked(st, cnt);
-            // bound centre (body frame) back into the shape frame, then the extents of the hull about it
-            float fr[7], cb[3];
-            for (int k = 0; k < 7; k++) fr[k] = d->env_shape_frame[(size_t)(7 * slot + k) * NE + e];
-            for (int k = 0; k < 3; k++) cb[k] = d->env_shape_bound[(size_t)(4 * slot + k) * NE + e] - fr[k];
-            const float nq = std::sqrt(fr[3] * fr[3] + fr[4] * fr[4] + fr[5] * fr[5] + fr[6] * fr[6]);
-            const float qw = fr[3] / nq, qx = fr[4] / nq, qy = fr[5] / nq, qz = fr[6] / nq;
-            const float R[3][3] = {{1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy)},
-                                   {2 * (qx * qy + qw * qz), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qw * qx)},
-                                   {2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), 1 - 2 * (qx * qx + qy * qy)}};
-            float cs[3];
-            for (int k = 0; k < 3; k++) cs[k] = R[0][k] * cb[0] + R[1][k] * cb[1] + R[2][k] * cb[2];
-            rows[0] = rows[1] = rows[2] = 0.f;
-            for (int i = 0; i < cnt; i++) {
-              const float* v = d->hull_verts + 3 * (size_t)(st + i);
-              for (int k = 0; k < 3; k++) rows[k] = std::max(rows[k], std::fabs(v[k] - cs[k]));
-            }
-            word |= (cnt << 3) | (found << 10);
-          }
-          float wf;
-          std::memcpy(&wf, &word, 4);
-          env_param_dev[(size_t)(4 * slot) * NE + e] = wf;
-          for (int k = 0; k < 3; k++) env_param_dev[(size_t)(4 * slot + 1 + k) * NE + e] = rows[k];
-        }
-      }
-    }
-    if (hv.size() / 3 >= (1u << 17)) { g_create_error = "too many hull vertices"; mssim_destroy(S); return 8; }
-    if ((rc = upload(S, sh.data(), sh.size(), &M.shape_hull)) || (rc = upload(S, hv.data(), hv.size(), &M.hull_verts))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-  }
-  if ((rc = upload(S, d->shape_body_kind, (size_t)ns, &M.shape_kind))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-  if ((rc = upload(S, d->shape_body_index, (size_t)ns, &M.shape_index))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-  if ((rc = upload(S, anc.data(), (size_t)n, &M.dof_anc))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-  {
-    std::vector<float> ctr(3 * (ns > 0 ? ns : 1), 0.f);
-    for (int s2 = 0; s2 < ns; s2++) {
-      const float* f = d->shape_frame + 7 * s2;
-      const float* b = d->shape_bound + 4 * s2;
-      const float w = f[3], x = f[4], y = f[5], z = f[6];
-      const float nq = std::sqrt(w * w + x * x + y * y + z * z);
-      const float qw = w / nq, qx = x / nq, qy = y / nq, qz = z / nq;
-      const float R[3][3] = {{1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy)},
-                             {2 * (qx * qy + qw * qz), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qw * qx)},
-                             {2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), 1 - 2 * (qx * qx + qy * qy)}};
-      for (int i = 0; i < 3; i++) ctr[3 * s2 + i] = f[i] + R[i][0] * b[0] + R[i][1] * b[1] + R[i][2] * b[2];
-    }
-    if ((rc = upload(S, ctr.data(), (size_t)3 * ns, &M.shape_center))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    // oriented bounding boxes for the cull (shape frame axes, centred at the bound centre)
-    std::vector<float> half(3 * (ns > 0 ? ns : 1), 0.f);
-    for (int s2 = 0; s2 < ns; s2++) {
-      const float* pp = d->shape_param + 4 * s2;
-      const float* b = d->shape_bound + 4 * s2;
-      float* h = &half[3 * s2];
-      switch (d->shape_type[s2]) {
-        case MSSIM_SHAPE_BOX: h[0] = pp[0]; h[1] = pp[1]; h[2] = pp[2]; break;
-        case MSSIM_SHAPE_SPHERE: h[0] = h[1] = h[2] = pp[0]; break;
-        case MSSIM_SHAPE_CAPSULE: h[0] = pp[1] + pp[0]; h[1] = h[2] = pp[0]; break;
-        case MSSIM_SHAPE_CYLINDER: h[0] = pp[1]; h[1] = h[2] = pp[0]; break;
-        case MSSIM_SHAPE_CONVEX:
-          for (int i = 0; i < d->shape_hull[2 * s2 + 1]; i++) {
-            const float* v = d->hull_verts + 3 * (size_t)(d->shape_hull[2 * s2] + i);
-            for (int k = 0; k < 3; k++) h[k] = std::max(h[k], std::fabs(v[k] - b[k]));
-          }
-          break;
-        case MSSIM_SHAPE_TRIMESH: {
-          const int first = (int)pp[0], count = (int)pp[1];
-          if (first < 0 || count < 0 || first + count > d->n_tri) { g_create_error = "triangle mesh: triangle range out of tri_soup"; mssim_destroy(S); return 8; }
-          for (int t = first; t < first + count; t++) {
-            const float* q = d->tri_soup + 12 * (size_t)t;
-            for (int c3 = 0; c3 < 3; c3++)
-              for (int k = 0; k < 3; k++) h[k] = std::max(h[k], std::fabs(q[k] + q[3 + 3 * c3 + k] - b[k]));
-          }
-          break;
-        }
-        default: h[0] = h[1] = h[2] = 3e30f;  // plane: never used
-      }
-      // primitive shapes are centred on their frame; keep the box valid if the bound centre is offset
-      if (d->shape_type[s2] != MSSIM_SHAPE_CONVEX && d->shape_type[s2] != MSSIM_SHAPE_PLANE && d->shape_type[s2] != MSSIM_SHAPE_TRIMESH)
-        for (int k = 0; k < 3; k++) h[k] += std::fabs(b[k]);
-    }
-    if ((rc = upload(S, half.data(), (size_t)3 * ns, &M.shape_half))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    if ((rc = upload(S, d->tri_soup, (size_t)12 * d->n_tri, &M.tri_soup)) || (rc = upload(S, d->tri_bvh, (size_t)112 * d->n_tri_node, &M.tri_bvh))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    // packed constant records (one or two cache lines per joint / shape instead of ~10 arrays)
-    auto fbits = [](int32_t v) { float f; std::memcpy(&f, &v, 4); return f; };
-    std::vector<float> sp(24 * (size_t)(ns > 0 ? ns : 1), 0.f);
-    for (int s2 = 0; s2 < ns; s2++) {
-      float* r = &sp[24 * (size_t)s2];
-      for (int k = 0; k < 7; k++) r[k] = d->shape_frame[7 * s2 + k];
-      for (int k = 0; k < 3; k++) { r[7 + k] = d->shape_param[4 * s2 + k]; r[10 + k] = ctr[3 * s2 + k]; r[14 + k] = half[3 * s2 + k]; }
-      r[13] = d->shape_bound[4 * s2 + 3];
-      r[17] = d->shape_material[4 * s2 + 1];
-      r[18] = fbits(d->shape_type[s2]);
-      r[19] = fbits(d->shape_body_kind[s2]);
-      r[20] = fbits(d->shape_body_index[s2]);
-      r[21] = fbits((d->n_env_shape > 0) ? d->shape_env_slot[s2] : -1);
-      r[22] = d->shape_material[4 * s2 + 3];  // torsional patch radius
-    }
-    if ((rc = upload(S, sp.data(), sp.size(), &M.shape_pack))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    S->h_dof_pack.assign(32 * (size_t)(n > 0 ? n : 1), 0.f);
-    for (int j = 0; j < n; j++) {
-      float* r = &S->h_dof_pack[32 * (size_t)j];
-      for (int k = 0; k < 7; k++) r[k] = d->dof_frame[7 * j + k];
-      for (int k = 0; k < 3; k++) r[7 + k] = d->dof_axis[3 * j + k];
-      r[10] = fbits(d->dof_parent[j]); r[11] = fbits(d->dof_type[j]); r[12] = fbits((int32_t)anc[j]);
-      for (int k = 0; k < 4; k++) r[13 + k] = d->dof_drive[4 * j + k];
-      r[17] = d->dof_armature[j]; r[18] = d->dof_limit[2 * j]; r[19] = d->dof_limit[2 * j + 1];
-      for (int k = 0; k < 10; k++) r[20 + k] = d->body_inertial[10 * j + k];
-      r[30] = fbits(d->body_gravity[j]);
-    }
-    if ((rc = upload(S, S->h_dof_pack.data(), S->h_dof_pack.size(), &M.dof_pack))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    S->d_dof_pack = const_cast<float*>(M.dof_pack);
-  }
-  {
-    const bool has_es = d->n_env_shape > 0, has_ef = d->n_env_free > 0;
-    if ((has_es || has_ef) && d->num_envs != num_envs) { g_create_error = "per-env arrays were built for a different num_envs"; mssim_destroy(S); return 7; }
-    std::vector<int32_t> sslot(ns > 0 ? ns : 1, -1), fslot(d->n_free > 0 ? d->n_free : 1, -1);
-    if (has_es) for (int i = 0; i < ns; i++) sslot[i] = d->shape_env_slot[i];
-    if (has_ef) for (int i = 0; i < d->n_free; i++) fslot[i] = d->free_env_slot[i];
-    if ((rc = upload(S, sslot.data(), sslot.size(), &M.shape_env_slot)) || (rc = upload(S, fslot.data(), fslot.size(), &M.free_env_slot)) ||
-        (rc = upload(S, d->env_shape_frame, (size_t)7 * d->n_env_shape * num_envs, &M.env_shape_frame)) ||
-        (rc = upload(S, has_es ? env_param_dev.data() : d->env_shape_param, (size_t)4 * d->n_env_shape * num_envs, &M.env_shape_param)) ||
-        (rc = upload(S, d->env_shape_bound, (size_t)4 * d->n_env_shape * num_envs, &M.env_shape_bound)) ||
-        (rc = upload(S, d->env_free_inertial, (size_t)10 * d->n_env_free * num_envs, &M.env_free_inertial))) {
-      mssim_destroy(S);
-      return rc;
-    }
-  }
-  S->d_drive = const_cast<float*>(M.dof_drive);
   M.gx = d->gravity[0]; M.gy = d->gravity[1]; M.gz = d->gravity[2];
   M.dt = d->timestep; M.contact_offset = d->contact_offset; M.rest_offset = d->rest_offset; M.erp = d->erp;
   M.max_depen = d->max_depenetration_velocity; M.pos_iters = d->position_iterations; M.vel_iters = d->velocity_iterations;
   M.sleep_threshold = d->sleep_threshold;
-  S->panda = (n == 9);
-  for (int j = 0; j < n && S->panda; j++)
-    if (d->dof_parent[j] != kPandaParent[j] || d->dof_type[j] != kPandaType[j]) S->panda = false;
+  up(d->dof_parent, n, &M.dof_parent); up(d->dof_type, n, &M.dof_type); up(d->dof_frame, 7 * n, &M.dof_frame); up(d->dof_axis, 3 * n, &M.dof_axis);
+  up(d->tendon_dof, 2 * (size_t)d->n_tendon, &M.tendon_dof); up(d->tendon_param, 5 * (size_t)d->n_tendon, &M.tendon_param);
+  up(d->link_body, d->n_link, &M.link_body); up(d->link_frame, 7 * (size_t)d->n_link, &M.link_frame);
+  up(d->free_inertial, 10 * nf, &M.free_inertial); up(d->free_damping, 2 * nf, &M.free_damping); up(d->free_gravity, nf, &M.free_gravity);
+  up(d->shape_row, ns, &M.shape_row); up(d->pair_shape, 2 * np, &M.pair_shape);
+  up(d->tri_soup, 12 * (size_t)d->n_tri, &M.tri_soup); up(d->tri_bvh, 112 * (size_t)d->n_tri_node, &M.tri_bvh);
+  up(d->env_shape_frame, 7 * d->n_env_shape * N, &M.env_shape_frame); up(d->env_shape_bound, 4 * d->n_env_shape * N, &M.env_shape_bound);
+  up(d->env_free_inertial, 10 * d->n_env_free * N, &M.env_free_inertial);
+  upv(P.dof_anc, &M.dof_anc); upv(P.dof_pack, &M.dof_pack); upv(P.shape_pack, &M.shape_pack);
+  upv(P.shape_hull, &M.shape_hull); upv(P.hull_verts, &M.hull_verts); upv(P.env_shape_param, &M.env_shape_param);
+  upv(P.free_env_slot, &M.free_env_slot); upv(P.pair_mesh_slot, &M.pair_mesh_slot); upv(P.pair_packed, &M.pair_packed);
+  S->h_dof_pack = std::move(P.dof_pack);
+  S->d_dof_pack = const_cast<float*>(M.dof_pack);
+  // tables from before shape_pack / dof_pack that no kernel reads
+  up(d->body_gravity, n, &M.body_gravity); up(d->dof_limit, 2 * n, &M.dof_limit); up(d->dof_drive, 4 * n, &M.dof_drive);
+  up(d->dof_armature, n, &M.dof_armature); up(d->body_inertial, 10 * n, &M.body_inertial);
+  up(d->shape_type, ns, &M.shape_type); up(d->shape_body_kind, ns, &M.shape_kind); up(d->shape_body_index, ns, &M.shape_index);
+  up(d->shape_frame, 7 * ns, &M.shape_frame); up(d->shape_param, 4 * ns, &M.shape_param); up(d->shape_material, 4 * ns, &M.shape_material);
+  up(d->shape_bound, 4 * ns, &M.shape_bound); up(P.shape_center.data(), 3 * ns, &M.shape_center); up(P.shape_half.data(), 3 * ns, &M.shape_half);
+  upv(P.shape_env_slot, &M.shape_env_slot);
+  S->d_drive = const_cast<float*>(M.dof_drive);
+
   DevState& D = S->S;
   D.N = num_envs;
-  const size_t N = (size_t)num_envs;
-#define AL(field, count) if ((rc = dalloc(S, (size_t)(count) * N, &D.field))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-  AL(root, 7) AL(q, n) AL(qd, n) AL(qt, n) AL(qdt, n) AL(qf, n) AL(qacc, n)
-  AL(free_s, 13 * d->n_free) AL(free_force, 3 * d->n_free) AL(kin, 7 * d->n_kin) AL(free_wake, d->n_free)
-  AL(bodypose, 7 * n) AL(bodyvel, 6 * n) AL(bodyaux, 6 * n)
-  AL(pair_cnt, d->n_pair) AL(pair_imp, 3 * d->n_pair)
-  if ((rc = dalloc(S, (size_t)num_envs * S16_ROWS_GLB * S16_ROWLEN_(S->rows_per_env), &D.rows))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-  AL(overflow, 1)
-  AL(hit_list, 1 + MAXC)
-  AL(pcm_tick, 1)
-  if ((rc = dalloc(S, (size_t)num_envs * MSSIM_PCM_SLOTS * S16_PCM_LEN, &D.pcm))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-#define HIPCHK_NEW(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_create_error = std::string(#call) + ": " + hipGetErrorString(_e); mssim_destroy(S); return 100 + (int)_e; } } while (0)
-  HIPCHK_NEW(hipMemset(D.pcm, 0xFF, (size_t)num_envs * MSSIM_PCM_SLOTS * S16_PCM_LEN * sizeof(float)));  // pair = -1: every slot empty
-  {
-    const size_t nw = (size_t)4 * (d->n_pair > 0 ? d->n_pair : 1) * N * 4;
-    if ((rc = dalloc(S, nw, &D.warm))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    HIPCHK_NEW(hipMemset(D.warm, 0xFF, nw * sizeof(float)));  // stamp -1: nothing to start from
-  }
-  {
-    // clearance of every (convex shape, mesh) pair (mssim_solve16.h stage T0); NaN bit pattern = no clearance known
-    std::vector<int32_t> slot((size_t)(d->n_pair > 0 ? d->n_pair : 1), -1);
-    int n_mesh_pair = 0;
-    for (int p = 0; p < d->n_pair; p++)
-      if (d->shape_type[d->pair_shape[2 * p + 1]] == MSSIM_SHAPE_TRIMESH) slot[p] = n_mesh_pair++;
-    if ((rc = upload(S, slot.data(), slot.size(), &M.pair_mesh_slot))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    std::vector<int32_t> packed((size_t)((d->n_pair + 127) / 128 * 128 + 128), -1);  // (read in chunks of 8 rounds of 16)
-    for (int p = 0; p < d->n_pair; p++) packed[p] = d->pair_shape[2 * p] | (d->pair_shape[2 * p + 1] << 8);
-    if ((rc = upload(S, packed.data(), packed.size(), &M.pair_packed))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    const size_t nc = (size_t)4 * (n_mesh_pair > 0 ? n_mesh_pair : 1) * N;
-    if ((rc = dalloc(S, nc, &D.tri_clear))) { g_create_error = S->err; mssim_destroy(S); return rc; }
-    HIPCHK_NEW(hipMemset(D.tri_clear, 0xFF, nc * sizeof(float)));
-#undef HIPCHK_NEW
-  }
-#undef AL
-  // identity quaternions
-  std::vector<float> ones(N, 1.0f);
-  hipMemcpy(D.root + 3 * N, ones.data(), N * sizeof(float), hipMemcpyHostToDevice);
-  for (int b = 0; b < d->n_free; b++) hipMemcpy(D.free_s + (13 * b + 3) * N, ones.data(), N * sizeof(float), hipMemcpyHostToDevice);
-  {
-    std::vector<float> awake(N * (size_t)(d->n_free > 0 ? d->n_free : 1), MSSIM_WAKE_TIME);
-    if (d->n_free > 0) hipMemcpy(D.free_wake, awake.data(), awake.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  for (int k = 0; k < d->n_kin; k++) hipMemcpy(D.kin + (7 * k + 3) * N, ones.data(), N * sizeof(float), hipMemcpyHostToDevice);
-  *out = S;
+  al(7 * N, &D.root); al(n * N, &D.q); al(n * N, &D.qd); al(n * N, &D.qt); al(n * N, &D.qdt); al(n * N, &D.qf); al(n * N, &D.qacc);
+  al(13 * nf * N, &D.free_s); al(3 * nf * N, &D.free_force); al(nf * N, &D.free_wake); al(7 * d->n_kin * N, &D.kin);
+  al(7 * n * N, &D.bodypose); al(6 * n * N, &D.bodyvel); al(6 * n * N, &D.bodyaux);
+  al(np * N, &D.pair_cnt); al(3 * np * N, &D.pair_imp); al((1 + MAXC) * N, &D.hit_list); al(N, &D.overflow); al(N, &D.pcm_tick);
+  al(N * S16_ROWS_GLB * S16_ROWLEN_(S->rows_per_env), &D.rows);
+  // caches start empty: manifold slots with pair = -1, multipliers with stamp = -1 (nothing to start from), and no
+  // clearance known for any (convex shape, mesh) pair (mssim_solve16.h stage T0)
+  const size_t n_pcm = N * MSSIM_PCM_SLOTS * S16_PCM_LEN, n_warm = 4 * (np > 0 ? np : 1) * N * 4, n_clear = 4 * (size_t)(P.n_mesh_pair > 0 ? P.n_mesh_pair : 1) * N;
+  al(n_pcm, &D.pcm); empty(D.pcm, n_pcm);
+  al(n_warm, &D.warm); empty(D.warm, n_warm);
+  al(n_clear, &D.tri_clear); empty(D.tri_clear, n_clear);
+  // identity quaternions; every free body awake
+  const std::vector<float> ones(N, 1.0f);
+  put(D.root, 3 * N, ones);
+  for (size_t b = 0; b < nf; b++) put(D.free_s, (13 * b + 3) * N, ones);
+  for (size_t k = 0; k < (size_t)d->n_kin; k++) put(D.kin, (7 * k + 3) * N, ones);
+  if (nf > 0) put(D.free_wake, 0, std::vector<float>(nf * N, MSSIM_WAKE_TIME));
+  if (rc) { g_create_error = S->err; return rc; }
+  *out = owner.release();
   return 0;
 }
 

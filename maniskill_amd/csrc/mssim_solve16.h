@@ -26,8 +26,8 @@
 // each, then the joint limits), so the parity tests cover every variant unchanged.
 // Requires n_dof <= 16, n_free <= 2, n_kin <= 6, n_shape <= 28 (mssim_create picks NR and says what a model exceeds).
 #pragma once
+#include "mssim_limits.h"  // S16_LANES, S16_MAX_FREE_, S16_MAX_KIN, S16_MAX_SHAPE_, S16_MAX_PAIR, S16_PCM_LEN, MAXC: shared with the host
 
-#define S16_LANES 16
 // A block is S16_WAVES waves of 4 envs each. Every wave works on its own envs (its own slice of the LDS, wave-level
 // ordering only: WSYNC) except in narrowphase stage B, where the generic-convex pairs of ALL the block's envs form one
 // task list taken round-robin by all its 16-lane groups (BSYNC = block barrier around it): the launch lasts as long as
@@ -50,12 +50,9 @@
 #define S16_PT 96      // pose table [23 + S16_MAX_FREE][7]: root | 16 links | the free bodies | 6 kinematic
 #define S16_PT_LINK 1
 #define S16_PT_FREE 17
-#define S16_MAX_FREE_(nr) ((nr) == 4 ? 6 : 2)  // free bodies per env: two per 16-lane row that holds free bodies
 #define S16_MAX_FREE S16_MAX_FREE_(NR)
 #define S16_PT_KIN_(nr) (S16_PT_FREE + S16_MAX_FREE_(nr))
 #define S16_PT_KIN S16_PT_KIN_(NR)
-#define S16_MAX_KIN 6
-#define S16_MAX_SHAPE_(nr) ((nr) == 4 ? 64 : ((nr) > 1 ? 48 : 28))  // shapes per model: a lane builds the world-table entries of two (NR > 1: all lanes of the env)
 #define S16_MAX_HIT 64
 #define S16_BP (S16_PT + 7 * S16_PT_LINK)  // link poses
 #define S16_U_(nr) ((nr) == 4 ? 320 : 272)  // union: dynamics staging | solver rows | narrowphase scratch
@@ -97,7 +94,7 @@
 #define S16_NP_HIT (S16_NP_B)        // [64] surviving pairs: pair | sa << 16 | sb << 24
 #define S16_NP_CNT (S16_NP_B + 64)   // [64] manifold sizes (raw, before the patch reduction)
 #define S16_NP_OFF (S16_NP_B + 128)  // [64] first point of each manifold in the point pool
-// [896]: pair table during the cull (<= 896 pairs) | [56][16] box-box clip scratch of the one-lane-per-pair path |
+// [896]: pair table during the cull (<= S16_MAX_PAIR pairs) | [56][16] box-box clip scratch of the one-lane-per-pair path |
 // afterwards the staged manifolds: normals, point pool, patch bookkeeping
 #define S16_NP_SCR (S16_NP_B + 192)
 #define S16_NP_HN (S16_NP_SCR)            // [64][3] manifold normals
@@ -111,10 +108,10 @@
 #define S16_NP_BL (S16_NP_B + 1104)  // [64 bytes] hit indices of this env's box-box pairs
 #define S16_NP_SLOT (S16_NP_B + 1120) // [64 bytes] persistent-manifold slot of each hit (255 none | slot | 0x80 newly assigned)
 #define S16_NP_PL (S16_NP_B + 1136)   // [64 bytes] hit indices of this env's (plane, hull) pairs
-#define S16_PCM_LEN 48            // floats per cache slot: pair npts stamp flags | relp(3) - | relR(9) n_loc(3) | 4 x (pA(3) pB(3) gap)
 #define S16_MAX_BBC 16            // box-box pairs per wave up to which they are worked on by 16-lane groups
 #define S16_MAX_MPR 64            // (= every hit: an arm folded onto itself and jammed into the table has 20+ hull pairs in range)
 static_assert(860 + 20 <= 896, "narrowphase staging exceeds the scratch area");
+static_assert(S16_MAX_PAIR <= 896, "the pair table of the cull exceeds the scratch area");
 static_assert(S16_NP_B_(1) + 1136 + 16 <= S16_REC_(1) && S16_NP_B_(2) + 1136 + 16 <= S16_REC_(2) && S16_NP_B_(4) + 1136 + 16 <= S16_REC_(4), "narrowphase lists run into the contact records");
 static_assert((S16_NP_B_(1) + 192 + 192) % 4 == 0 && (S16_NP_B_(2) + 192 + 192) % 4 == 0 && (S16_NP_B_(4) + 192 + 192) % 4 == 0, "point pool: 16-byte aligned");
 static_assert(S16_PT + 7 * (S16_PT_KIN_(1) + S16_MAX_KIN) <= S16_U_(1) && S16_PT + 7 * (S16_PT_KIN_(4) + S16_MAX_KIN) <= S16_COM_(4) && S16_COM_(4) + 18 <= S16_U_(4), "pose table runs into the union");
