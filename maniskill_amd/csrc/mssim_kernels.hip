@@ -22,6 +22,8 @@
 #include <algorithm>
 #include <memory>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mssim.h"
@@ -958,6 +960,21 @@ __global__ void k_i2f(const int* src, float* dst, size_t count) {
 // host side
 #include "mssim_solve16.h"
 #include "mssim_model_pack.h"
+#include "mssim_dispatch.h"
+
+// every compiled instance of the control-step kernel, in the order of mssim_dispatch::kInstances
+using solve16_fn = void (*)(DevModel, DevState, int);
+#define MSSIM_SOLVE16_FN_(NDOF, TASK, TRI, NR) k_solve16<NDOF, TASK, TRI, NR>,
+static const solve16_fn kSolve16[] = {MSSIM_SOLVE16_INSTANCES(MSSIM_SOLVE16_FN_)};
+#undef MSSIM_SOLVE16_FN_
+static_assert(S16_ENVS_PER_BLOCK == 4, "mssim_dispatch::tail_fits counts waves of 4 envs");
+
+// What is owed to the next call on the handle (settle() performs it). mssim_defer_step_action: a step_action; a task
+// epilogue runs it, the copy-out and itself as ONE launch of the control-step kernel. mssim_defer_fetch: a copy-out.
+struct Owed {
+  const float* action = nullptr; int adim = 0, nsub = 0; hipStream_t stream = nullptr;
+  unsigned fetch = 0u;
+};
 
 struct mssim_sim {
   int device = 0;
@@ -973,22 +990,24 @@ struct mssim_sim {
   int rows_per_env = 1;  // 16-lane rows an env takes in the control-step kernel (its template parameter NR): 2 when the model has more than 16 velocity components
   bool dirty = true;
   int n_cu = 256;  // compute units of the device
-  unsigned deferred_fetch = 0u;  // mssim_defer_fetch: copy-out owed to the next call on the handle
-  // mssim_defer_step_action: a step_action owed to the next call; a task epilogue runs it, the copy-out and
-  // itself as ONE launch of the control-step kernel
-  const float* deferred_action = nullptr; int deferred_adim = 0, deferred_nsub = 0; hipStream_t deferred_stream = nullptr;
+  // the control-step kernel of this model (mssim_dispatch.h, resolved by mssim_create): the plain step, and per task id
+  // the instance with that task's epilogue at its tail (null: the epilogue is a launch of its own)
+  solve16_fn step_fn = nullptr, tail_fn[mssim_dispatch::kNumTasks] = {};
+  dim3 step_grid;
+  Owed owed;
   std::vector<float> h_dof_pack; float* d_dof_pack = nullptr;  // (drive gains are patched by set_drive_properties)
   std::vector<int32_t> h_shape_row, h_pair_shape;  // host copies (contact-pair lists of the task epilogues)
-  int* d_pick_pairs = nullptr; int n_pick_pairs = 0; int pick_rows[3] = {-1, -1, -1};
+  // finger <-> object candidate pairs of the task epilogue that asked last, and the (object, finger, finger) rows they are for
+  int* d_finger_pairs = nullptr; int n_finger_pairs = 0; int finger_pair_rows[3] = {-1, -1, -1};
   long long n_tail_steps = 0;  // control steps that ran with the task epilogue at the kernel's tail (mssim_tail_step_count)
   std::vector<int*> queries;
   std::vector<int> query_n;
   std::vector<int> query_kind;
   std::string err;
-  // profiling (bench roofline block): event pairs recorded on the launch stream
   int* d_act_col = nullptr; float* d_act_lo = nullptr; float* d_act_hi = nullptr; int* d_act_flags = nullptr;
   EeMap ee{-1, 0, 3, 0.f, 0.f, 0.f, 0};
   int act_max_col = -1;  // highest action column the joint map reads
+  // profiling (bench roofline block): event pairs recorded on the launch stream
   bool profiling = false;
   std::vector<hipEvent_t> ev[2];  // [kernel] start/stop interleaved
   size_t ev_used[2] = {0, 0};
@@ -1034,6 +1053,25 @@ static int dset(mssim_sim* S, float* dst, int byte, size_t count) {
 static int dput(mssim_sim* S, float* dst, const std::vector<float>& v) {
   HIPCHK(S, hipMemcpy(dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
   return 0;
+}
+
+static inline int pad8(int n) { return (n + 7) / 8 * 8; }
+static inline dim3 env_grid(int N, int block) { return dim3(pad8((N + block - 1) / block)); }  // kernels map blocks with xcd_chunk
+
+// The kernel pointers of the model's control step. find_instance(plain) is never -1: mssim_dispatch.h proves at compile
+// time (plain_steps_compiled) that the list holds plain_step() of every model with at most 16 joints and 1, 2 or 4 rows,
+// which is all validate_model (mssim_model_pack.h) lets through -- relax that limit and that proof together. A tail has
+// the rows per env, so the grid, of the plain step.
+static void resolve_control_step(mssim_sim* S, int n_dof) {
+  using namespace mssim_dispatch;
+  static_assert(S16_LANES == 16, "plain_steps_compiled() covers n_dof <= 16");
+  const Key plain = plain_step(n_dof, S->rows_per_env, S->has_tri);
+  S->step_fn = kSolve16[find_instance(plain)];
+  S->step_grid = env_grid(S->N, S16_WAVES * S16_ENVS_PER_BLOCK / plain.nr);
+  for (int task = 1; task < kNumTasks; task++) {
+    const Key tail = tail_step(task, n_dof, S->rows_per_env, S->has_tri, S->N, S->n_cu);
+    if (!(tail == kNone)) S->tail_fn[task] = kSolve16[find_instance(tail)];
+  }
 }
 
 extern "C" {
@@ -1128,20 +1166,21 @@ int mssim_create(const mssim_model_desc* d, int32_t num_envs, int32_t device, ms
   for (size_t k = 0; k < (size_t)d->n_kin; k++) put(D.kin, (7 * k + 3) * N, ones);
   if (nf > 0) put(D.free_wake, 0, std::vector<float>(nf * N, MSSIM_WAKE_TIME));
   if (rc) { g_create_error = S->err; return rc; }
+  resolve_control_step(S, d->n_dof);
   *out = owner.release();
   return 0;
 }
 
-static void flush_deferred(mssim_handle h, hipStream_t st);
+static void settle(mssim_handle h, hipStream_t st, bool keep_fetch = false);
 int mssim_bind_buffers(mssim_handle h, const mssim_buffers* b) {
-  if (h) flush_deferred(h, (hipStream_t)0);
+  if (h) settle(h, (hipStream_t)0);
   if (!h || !b) return 1;
   h->buf = *b;
   return 0;
 }
 
 int mssim_set_timestep(mssim_handle h, float dt) {
-  flush_deferred(h, h->deferred_stream);
+  settle(h, h->owed.stream);
   if (!(dt > 0.f)) { h->err = "timestep must be positive"; return 1; }
   h->M.dt = dt;
   return 0;
@@ -1149,7 +1188,7 @@ int mssim_set_timestep(mssim_handle h, float dt) {
 float mssim_get_timestep(mssim_handle h) { return h->M.dt; }
 
 int mssim_set_drive_properties(mssim_handle h, const float* drive) {
-  flush_deferred(h, h->deferred_stream);
+  settle(h, h->owed.stream);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipMemcpy(h->d_drive, drive, sizeof(float) * 4 * h->M.n_dof, hipMemcpyHostToDevice));
   for (int j = 0; j < h->M.n_dof; j++)
@@ -1158,38 +1197,25 @@ int mssim_set_drive_properties(mssim_handle h, const float* drive) {
   return 0;
 }
 
-static inline int pad8(int n) { return (n + 7) / 8 * 8; }
-static inline dim3 env_grid(int N, int block) { return dim3(pad8((N + block - 1) / block)); }  // kernels map blocks with xcd_chunk
-
 int mssim_apply(mssim_handle h, uint32_t what, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   hipLaunchKernelGGL(k_apply, env_grid(h->N, 256), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what);
   h->dirty = true;
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
-// Deferred fetch (mssim_defer_fetch): the copy-out is owed until the next call on the handle. A task epilogue
-// performs it inside its own launch (k_task_*<true>); every other entry point that touches the state or
-// the buffers performs it first, so the deferral is only an ordering of launches, never a change of results.
-static unsigned take_deferred_fetch(mssim_handle h) {
-  const unsigned w = h->deferred_fetch;
-  h->deferred_fetch = 0u;
-  return w;
-}
-static void flush_deferred_fetch(mssim_handle h, hipStream_t st) {
-  if (const unsigned w = take_deferred_fetch(h))
-    hipLaunchKernelGGL(k_fetch, dim3(pad8((h->N + 63) / 64), h->M.n_link + h->M.n_free + h->M.n_kin + 1), dim3(64), 0, st, h->M, h->S, h->buf, w);
+static void launch_fetch(mssim_handle h, unsigned what, hipStream_t st) {
+  hipLaunchKernelGGL(k_fetch, dim3(pad8((h->N + 63) / 64), h->M.n_link + h->M.n_free + h->M.n_kin + 1), dim3(64), 0, st, h->M, h->S, h->buf, what);
 }
 int mssim_defer_fetch(mssim_handle h, uint32_t what) {
-  h->deferred_fetch |= what;
+  h->owed.fetch |= what;
   return 0;
 }
 
 int mssim_fetch(mssim_handle h, uint32_t what, void* stream) {
-  what |= take_deferred_fetch(h);
-  flush_deferred(h, (hipStream_t)stream);
-  hipLaunchKernelGGL(k_fetch, dim3(pad8((h->N + 63) / 64), h->M.n_link + h->M.n_free + h->M.n_kin + 1), dim3(64), 0, (hipStream_t)stream, h->M, h->S, h->buf, what);
+  settle(h, (hipStream_t)stream, /*keep_fetch=*/true);  // the owed copy-out joins this one
+  launch_fetch(h, what | std::exchange(h->owed.fetch, 0u), (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -1198,9 +1224,12 @@ static void launch_fk(mssim_handle h, hipStream_t st) {
   if (h->panda) hipLaunchKernelGGL(k_fk<TopoPanda>, env_grid(h->N, 64), dim3(64), 0, st, h->M, h->S);
   else hipLaunchKernelGGL(k_fk<TopoDyn>, env_grid(h->N, 64), dim3(64), 0, st, h->M, h->S);
 }
+static void fk_if_dirty(mssim_handle h, hipStream_t st) {
+  if (h->dirty) { launch_fk(h, st); h->dirty = false; }
+}
 
 int mssim_wake_all(mssim_handle h, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   const size_t cnt = (size_t)h->M.n_free * h->N;
   if (cnt > 0) hipLaunchKernelGGL(k_fill, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->S.free_wake, MSSIM_WAKE_TIME, cnt);
   HIPCHK(h, hipMemsetAsync(h->S.pcm, 0xFF, (size_t)h->N * MSSIM_PCM_SLOTS * S16_PCM_LEN * sizeof(float), (hipStream_t)stream));  // every slot empty
@@ -1221,7 +1250,7 @@ __global__ void k_wake_envs(DevModel M, DevState S, const long long* __restrict_
   for (int k = threadIdx.x; k < 4 * M.n_pair; k += blockDim.x) reinterpret_cast<int*>(S.warm)[((size_t)k * N + e) * 4 + 3] = -1;  // stamp -1
 }
 int mssim_wake_envs(mssim_handle h, const int64_t* env_idx, int32_t n_idx, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   if (n_idx <= 0) return 0;
   if (!env_idx) { h->err = "wake_envs: no index array"; return 1; }
   hipLaunchKernelGGL(k_wake_envs, dim3((unsigned)n_idx), dim3(256), 0, (hipStream_t)stream, h->M, h->S, reinterpret_cast<const long long*>(env_idx), (int)n_idx);
@@ -1230,7 +1259,7 @@ int mssim_wake_envs(mssim_handle h, const int64_t* env_idx, int32_t n_idx, void*
 }
 
 int mssim_update_kinematics(mssim_handle h, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   launch_fk(h, (hipStream_t)stream);
   h->dirty = false;
   HIPCHK(h, hipGetLastError());
@@ -1242,71 +1271,23 @@ static inline void prof_mark(mssim_handle h, int k, hipStream_t st) {
   (void)hipEventRecord(h->ev[k][h->ev_used[k]++], st);
 }
 
-extern "C++" {
-template <int TASK>
-static void launch_control_step(mssim_handle h, const DevState& S, int n_substeps, hipStream_t st);
+// one control step: `k` is the handle's step_fn or one of its tail_fn (whose epilogue reads S.tail_*)
+static void launch_control_step(mssim_handle h, solve16_fn k, const DevState& S, int n_substeps, hipStream_t st) {
+  prof_mark(h, 0, st);
+  hipLaunchKernelGGL(k, h->step_grid, dim3(64 * S16_WAVES), 0, st, h->M, S, n_substeps);
+  prof_mark(h, 0, st);
 }
-int mssim_step(mssim_handle h, int32_t n_substeps, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
-  hipStream_t st = (hipStream_t)stream;
-  if (h->dirty) { launch_fk(h, st); h->dirty = false; }
-  if (n_substeps > 0) launch_control_step<0>(h, h->S, (int)n_substeps, st);
+static int step_now(mssim_handle h, const DevState& S, int n_substeps, hipStream_t st) {
+  fk_if_dirty(h, st);
+  if (n_substeps > 0) launch_control_step(h, h->step_fn, S, n_substeps, st);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
-
-// TASK: 0 = plain control step, 1 / 2 / 3 = copy-out + PickCube / PushCube / PegInsertionSide epilogue at its tail (one row per
-// env), 4 = copy-out + StackCube epilogue (two rows per env: the Panda with two cubes), 5 = copy-out + PushT epilogue (one row:
-// the 7-joint panda_stick and the T block, 13 velocity components)
-extern "C++" {
-template <int TASK>
-static void launch_control_step(mssim_handle h, const DevState& S, int n_substeps, hipStream_t st) {
-  prof_mark(h, 0, st);
-  const dim3 block(64 * S16_WAVES);
-#ifdef MSSIM_ONLY_PANDA
-  // (timing experiments, scripts/ab_variants.sh: only the benchmark's instances are compiled -- a fifth of the build time)
-  // (TASK 4 and 5 are not among them: control_step_with_task leaves StackCube and PushT to the separate epilogue launch in
-  // this build)
-  hipLaunchKernelGGL((k_solve16<9, (TASK == 4 || TASK == 5) ? 0 : TASK>), env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK), block, 0, st, h->M, S, n_substeps);
-#else
-  if (h->rows_per_env == 4) {  // three to six free bodies: four 16-lane rows (a whole wave) per env, 4 envs per block; the generic-topology instances
-    const dim3 grid4 = env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK / 4);
-    if (h->has_tri) hipLaunchKernelGGL((k_solve16<0, 0, true, 4>), grid4, block, 0, st, h->M, S, n_substeps);
-    else hipLaunchKernelGGL((k_solve16<0, 0, false, 4>), grid4, block, 0, st, h->M, S, n_substeps);
-    prof_mark(h, 0, st);
-    return;
-  }
-  if (h->rows_per_env == 2) {  // more than 16 velocity components: two 16-lane rows per env, 8 envs per block
-    const dim3 grid2 = env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK / 2);
-    if (h->has_tri) {
-      if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, 0, true, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-      else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0, true, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-      else hipLaunchKernelGGL((k_solve16<0, 0, true, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-    } else if (h->M.n_dof == 9) {
-      if (TASK == 4) hipLaunchKernelGGL((k_solve16<9, 4, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-      else hipLaunchKernelGGL((k_solve16<9, 0, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-    }
-    else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-    else hipLaunchKernelGGL((k_solve16<0, 0, false, 2>), grid2, block, 0, st, h->M, S, n_substeps);
-    prof_mark(h, 0, st);
-    return;
-  }
-  const dim3 grid = env_grid(h->N, S16_WAVES * S16_ENVS_PER_BLOCK);
-  if (h->has_tri) {  // models with triangle meshes: the variant that carries the mesh stage (never with a task tail)
-    if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
-    else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
-    else hipLaunchKernelGGL((k_solve16<0, 0, true>), grid, block, 0, st, h->M, S, n_substeps);
-  } else if (h->M.n_dof == 9) hipLaunchKernelGGL((k_solve16<9, (TASK == 4 || TASK == 5) ? 0 : TASK>), grid, block, 0, st, h->M, S, n_substeps);
-  else if (h->M.n_dof == 7) {  // (panda_stick; the plain instance keeps the physics of fused and unfused runs the same)
-    if (TASK == 5) hipLaunchKernelGGL((k_solve16<7, 5>), grid, block, 0, st, h->M, S, n_substeps);
-    else hipLaunchKernelGGL((k_solve16<7, 0>), grid, block, 0, st, h->M, S, n_substeps);
-  }
-  else if (h->M.n_dof == 15) hipLaunchKernelGGL((k_solve16<15, 0>), grid, block, 0, st, h->M, S, n_substeps);  // (the Fetch)
-  else hipLaunchKernelGGL((k_solve16<0, 0>), grid, block, 0, st, h->M, S, n_substeps);
-#endif
-  prof_mark(h, 0, st);
+int mssim_step(mssim_handle h, int32_t n_substeps, void* stream) {
+  settle(h, (hipStream_t)stream);
+  return step_now(h, h->S, (int)n_substeps, (hipStream_t)stream);
 }
-}  // extern "C++"
+
 static DevState state_with_action(mssim_handle h, const float* action, int action_dim) {
   DevState S = h->S;
   S.act = action; S.act_dim = action_dim;
@@ -1324,45 +1305,48 @@ static int check_action_dim(mssim_handle h, int32_t action_dim) {
   }
   return 0;
 }
+static void launch_apply_action(mssim_handle h, const float* action, int action_dim, hipStream_t st) {
+  hipLaunchKernelGGL(k_apply_action, env_grid(h->N, 256), dim3(256), 0, st, h->M, h->S, h->buf, action, action_dim,
+                     h->d_act_col, h->d_act_lo, h->d_act_hi, h->d_act_flags, h->ee);
+}
 static int step_action_now(mssim_handle h, const float* action, int32_t action_dim, int32_t n_substeps, hipStream_t st) {
   if (n_substeps <= 0 || h->ee.link >= 0) {  // end-effector block: apply_action, then step
-    hipLaunchKernelGGL(k_apply_action, env_grid(h->N, 256), dim3(256), 0, st, h->M, h->S, h->buf, action, action_dim,
-                       h->d_act_col, h->d_act_lo, h->d_act_hi, h->d_act_flags, h->ee);
-    return mssim_step(h, n_substeps, st);
+    launch_apply_action(h, action, action_dim, st);
+    return step_now(h, h->S, n_substeps, st);
   }
-  if (h->dirty) { launch_fk(h, st); h->dirty = false; }
-  launch_control_step<0>(h, state_with_action(h, action, action_dim), n_substeps, st);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return step_now(h, state_with_action(h, action, action_dim), n_substeps, st);
 }
-// everything owed to the handle (see mssim_defer_step_action / mssim_defer_fetch), in order
-static void flush_deferred(mssim_handle h, hipStream_t st) {
-  if (h->deferred_action) {
-    const float* a = h->deferred_action;
-    h->deferred_action = nullptr;
-    (void)step_action_now(h, a, h->deferred_adim, h->deferred_nsub, h->deferred_stream);
+// Everything owed to the handle, in order: the step on the stream it was deferred on, then the copy-out on `st`. Every
+// entry point that touches the state or the buffers calls this first, so a deferral is only an ordering of launches,
+// never a change of results. `keep_fetch`: the copy-out stays owed to the caller, which performs it inside its own
+// launch (a task epilogue: k_task_*<true>).
+static void settle(mssim_handle h, hipStream_t st, bool keep_fetch) {
+  if (h->owed.action) {
+    const float* a = h->owed.action;
+    h->owed.action = nullptr;
+    (void)step_action_now(h, a, h->owed.adim, h->owed.nsub, h->owed.stream);
   }
-  flush_deferred_fetch(h, st);
+  if (!keep_fetch && h->owed.fetch) launch_fetch(h, std::exchange(h->owed.fetch, 0u), st);
 }
 
 int mssim_step_action(mssim_handle h, const float* action, int32_t action_dim, int32_t n_substeps, void* stream) {
   if (int rc = check_action_dim(h, action_dim)) return rc;
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   return step_action_now(h, action, action_dim, n_substeps, (hipStream_t)stream);
 }
 
 int mssim_defer_step_action(mssim_handle h, const float* action, int32_t action_dim, int32_t n_substeps, void* stream) {
   if (int rc = check_action_dim(h, action_dim)) return rc;
-  flush_deferred(h, (hipStream_t)stream);
-  h->deferred_action = action; h->deferred_adim = action_dim; h->deferred_nsub = n_substeps; h->deferred_stream = (hipStream_t)stream;
+  settle(h, (hipStream_t)stream);
+  h->owed.action = action; h->owed.adim = action_dim; h->owed.nsub = n_substeps; h->owed.stream = (hipStream_t)stream;
   return 0;
 }
 
 int mssim_link_jacobian(mssim_handle h, int32_t link_index, float* out, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   if (link_index < 0 || link_index >= h->M.n_link || !out) { h->err = "link_jacobian: bad link index / output"; return 1; }
   hipStream_t st = (hipStream_t)stream;
-  if (h->dirty) { launch_fk(h, st); h->dirty = false; }
+  fk_if_dirty(h, st);
   hipLaunchKernelGGL(k_link_jacobian, env_grid(h->N, 256), dim3(256), 0, st, h->M, h->S, (int)link_index, out);
   HIPCHK(h, hipGetLastError());
   return 0;
@@ -1382,7 +1366,7 @@ int mssim_profile_enable(mssim_handle h, int32_t on) {
 }
 
 int mssim_profile_read(mssim_handle h, float* out_ms, int32_t* out_counts) {
-  flush_deferred(h, h->deferred_stream);
+  settle(h, h->owed.stream);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipDeviceSynchronize());
   for (int k = 0; k < 2; k++) {
@@ -1401,7 +1385,7 @@ int mssim_profile_read(mssim_handle h, float* out_ms, int32_t* out_counts) {
 }
 
 int mssim_set_action_map(mssim_handle h, const int32_t* column, const float* low, const float* high, const int32_t* flags) {
-  flush_deferred(h, h->deferred_stream);
+  settle(h, h->owed.stream);
   HIPCHK(h, hipSetDevice(h->device));
   const int n = h->M.n_dof > 0 ? h->M.n_dof : 1;
   for (int j = 0; j < h->M.n_dof; j++)
@@ -1420,17 +1404,16 @@ int mssim_set_action_map(mssim_handle h, const int32_t* column, const float* low
 }
 
 int mssim_set_ee_action_map(mssim_handle h, int32_t link_index, int32_t column0, int32_t rows, float low, float high, float rot_scale, int32_t flags) {
-  flush_deferred(h, h->deferred_stream);
+  settle(h, h->owed.stream);
   if (link_index >= h->M.n_link || (link_index >= 0 && rows != 3 && rows != 6)) { h->err = "set_ee_action_map: bad link index / rows"; return 1; }
   h->ee = EeMap{link_index < 0 ? -1 : (int)link_index, (int)column0, (int)rows, low, high, rot_scale, (int)flags};
   return 0;
 }
 
 int mssim_apply_action(mssim_handle h, const float* action, int32_t action_dim, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   if (int rc = check_action_dim(h, action_dim)) return rc;
-  hipLaunchKernelGGL(k_apply_action, env_grid(h->N, 256), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, action, action_dim,
-                     h->d_act_col, h->d_act_lo, h->d_act_hi, h->d_act_flags, h->ee);
+  launch_apply_action(h, action, action_dim, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -1438,7 +1421,7 @@ int mssim_apply_action(mssim_handle h, const float* action, int32_t action_dim, 
 // candidate finger <-> object pairs (a handful of the ~100 pairs of the scene) for the task epilogues:
 // entry = pair | finger (bit 30: 0 left, 1 right) | object is shape A (bit 31); cached per (object, fingers)
 static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row) {
-  if (h->pick_rows[0] == obj_row && h->pick_rows[1] == f1_row && h->pick_rows[2] == f2_row && h->d_pick_pairs) return 0;
+  if (h->finger_pair_rows[0] == obj_row && h->finger_pair_rows[1] == f1_row && h->finger_pair_rows[2] == f2_row && h->d_finger_pairs) return 0;
   std::vector<int32_t> lst;
   for (int p = 0; p < h->M.n_pair; p++) {
     const int ra = h->h_shape_row[h->h_pair_shape[2 * p]], rb = h->h_shape_row[h->h_pair_shape[2 * p + 1]];
@@ -1449,158 +1432,116 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
     lst.push_back((int32_t)((unsigned)p | (other == f2_row ? 1u << 30 : 0u) | (a_obj ? 1u << 31 : 0u)));
   }
   HIPCHK(h, hipSetDevice(h->device));
-  if (!h->d_pick_pairs) { HIPCHK(h, hipMalloc((void**)&h->d_pick_pairs, sizeof(int32_t) * (h->M.n_pair > 0 ? h->M.n_pair : 1))); h->allocs.push_back(h->d_pick_pairs); }
-  if (!lst.empty()) HIPCHK(h, hipMemcpy(h->d_pick_pairs, lst.data(), sizeof(int32_t) * lst.size(), hipMemcpyHostToDevice));
-  h->n_pick_pairs = (int)lst.size();
-  h->pick_rows[0] = obj_row; h->pick_rows[1] = f1_row; h->pick_rows[2] = f2_row;
+  if (!h->d_finger_pairs) { HIPCHK(h, hipMalloc((void**)&h->d_finger_pairs, sizeof(int32_t) * (h->M.n_pair > 0 ? h->M.n_pair : 1))); h->allocs.push_back(h->d_finger_pairs); }
+  if (!lst.empty()) HIPCHK(h, hipMemcpy(h->d_finger_pairs, lst.data(), sizeof(int32_t) * lst.size(), hipMemcpyHostToDevice));
+  h->n_finger_pairs = (int)lst.size();
+  h->finger_pair_rows[0] = obj_row; h->finger_pair_rows[1] = f1_row; h->finger_pair_rows[2] = f2_row;
   return 0;
 }
 
-// A deferred step_action + deferred fetch + this epilogue = one launch of the control-step kernel (Panda
-// models: the task tail is compiled into k_solve16<9, TASK> for one row per env, k_solve16<9, 4, false, 2> for
-// StackCube's two). Returns false if that does not apply.
+// A task epilogue, the one sequence behind the five mssim_task_*_outputs. Refusals come first and leave what is owed owed.
+// An owed step_action + an owed fetch + the epilogue = ONE launch of the control-step kernel, where mssim_create found an
+// instance with the task's tail for the model (h->tail_fn). Otherwise what is owed is performed and the epilogue is a launch
+// of its own: `standalone(std::true_type, what, st)` launches k_task_*<true>, which first performs the owed copy-out `what`,
+// `standalone(std::false_type, 0, st)` launches k_task_*<false>.
+struct TaskCall {
+  int id; const char* name;  // mssim_dispatch::Task and its name in the messages
+  const char* refused;       // the task's own check failed: its message (rc 3); else null
+  const int* pair_rows;      // (object, finger 1, finger 2) rows of the contact pairs the task reads, or null
+  float *obs, *reward; uint8_t* flags;
+  float* extra;              // DevState::tail_head, or null
+};
 extern "C++" {
-template <int TASK>
-static bool control_step_with_task(mssim_handle h, DevState& S, hipStream_t st) {
-  const int ndof = TASK == 5 ? 7 : 9;  // the joints the task's tail is compiled for (PushT: panda_stick)
-  if (!(h->deferred_action && h->deferred_fetch && h->M.n_dof == ndof && h->deferred_nsub > 0 && st == h->deferred_stream && h->ee.link < 0) || h->has_tri) return false;
-  const int rows = TASK == 4 ? 2 : 1;  // the rows per env the task's tail is compiled for
-#ifdef MSSIM_ONLY_PANDA
-  if (rows != 1 || TASK == 5) return false;  // (only the Panda's one-row instances are compiled)
-#endif
-  if (h->rows_per_env != rows) return false;
-  // The tail runs at the kernel's one wave per SIMD: worth it while all blocks are resident at once (4 per CU) and
-  // the launch is latency-bound anyway; with more blocks the separate, fully occupied copy-out + epilogue launch
-  // is cheaper than a tail per block.
-  if (rows == 1 && (h->N + S16_ENVS_PER_BLOCK - 1) / S16_ENVS_PER_BLOCK > 4 * h->n_cu) return false;
-  // Two rows: blocks of 8 envs, the same count of blocks (N <= 8192 on 256 CUs). Measured (StackCube, 4096 envs, 1000
-  // unreset steps): 0.947 ms per step with the tail, 0.963 ms with the separate launch.
-  if (rows == 2 && (h->N + 7) / 8 > 4 * h->n_cu) return false;
-  const DevState A = state_with_action(h, h->deferred_action, h->deferred_adim);
-  S.act = A.act; S.act_dim = A.act_dim; S.act_col = A.act_col; S.act_lo = A.act_lo; S.act_hi = A.act_hi; S.act_flags = A.act_flags;
-  S.act_qpos = A.act_qpos; S.act_target = A.act_target; S.act_target_vel = A.act_target_vel;
-  S.tail_fetch = take_deferred_fetch(h);
-  S.tail_buf = h->buf;
-  h->deferred_action = nullptr;
-  if (h->dirty) { launch_fk(h, st); h->dirty = false; }
-  launch_control_step<TASK>(h, S, h->deferred_nsub, st);
-  h->n_tail_steps++;
-  return true;
+using TailTask = decltype(DevState::tail_task);
+// rows: the body rows the task reads; slot: the task's member of the tail_task union
+template <class Task, size_t NROWS, class Standalone>
+static int task_outputs(mssim_handle h, const TaskCall& c, Task TailTask::*slot, const Task* task, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
+  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
+  for (int r : rows)
+    if (r < 0 || r >= R) { h->err = std::string("task_") + c.name + "_outputs: body row out of range"; return 1; }
+  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
+  if (c.refused) { h->err = c.refused; return 3; }
+  if (c.pair_rows)
+    if (int rc = finger_pair_list(h, c.pair_rows[0], c.pair_rows[1], c.pair_rows[2])) return rc;
+  const Owed& o = h->owed;
+  if (h->tail_fn[c.id] && o.action && o.fetch && o.nsub > 0 && st == o.stream && h->ee.link < 0) {
+    DevState S = state_with_action(h, o.action, o.adim);
+    S.tail_task.*slot = *task;
+    S.tail_pairs = c.pair_rows ? h->d_finger_pairs : nullptr; S.tail_npairs = c.pair_rows ? h->n_finger_pairs : 0;
+    S.tail_obs = c.obs; S.tail_reward = c.reward; S.tail_flags = c.flags; S.tail_head = c.extra;
+    S.tail_fetch = std::exchange(h->owed.fetch, 0u);
+    S.tail_buf = h->buf;
+    h->owed.action = nullptr;
+    fk_if_dirty(h, st);
+    launch_control_step(h, h->tail_fn[c.id], S, o.nsub, st);
+    h->n_tail_steps++;
+  } else {
+    settle(h, st, /*keep_fetch=*/true);
+    if (const unsigned what = std::exchange(h->owed.fetch, 0u)) standalone(std::true_type{}, what, st);
+    else standalone(std::false_type{}, 0u, st);
+  }
+  HIPCHK(h, hipGetLastError());
+  return 0;
 }
 }  // extern "C++"
 
-int mssim_task_peg_outputs(mssim_handle h, const mssim_peg_task* task, float* obs, float* reward, uint8_t* flags, float* head_at_hole, void* stream) {
-  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
-  const int rows[5] = {task->tcp_row, task->peg_row, task->box_row, task->finger1_row, task->finger2_row};
-  for (int r : rows)
-    if (r < 0 || r >= R) { h->err = "task_peg_outputs: body row out of range"; return 1; }
-  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
-  if (!task->peg_half_sizes || !task->box_hole_offsets || !task->box_hole_radii || !head_at_hole) { h->err = "task_peg_outputs: missing per-env geometry / output"; return 3; }
-  { int rc = finger_pair_list(h, task->peg_row, task->finger1_row, task->finger2_row); if (rc) return rc; }
-  {
-    DevState S = h->S;
-    S.tail_task.peg = *task; S.tail_pairs = h->d_pick_pairs; S.tail_npairs = h->n_pick_pairs;
-    S.tail_obs = obs; S.tail_reward = reward; S.tail_flags = flags; S.tail_head = head_at_hole;
-    if (control_step_with_task<3>(h, S, (hipStream_t)stream)) { HIPCHK(h, hipGetLastError()); return 0; }
-  }
-  if (h->deferred_action) { const unsigned w = take_deferred_fetch(h); flush_deferred(h, (hipStream_t)stream); h->deferred_fetch = w; }
-  if (const unsigned what = take_deferred_fetch(h))
-    hipLaunchKernelGGL(k_task_peg<true>, env_grid(h->N, 64), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags, head_at_hole);
-  else
-    hipLaunchKernelGGL(k_task_peg<false>, env_grid(h->N, 64), dim3(64), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags, head_at_hole);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-
-int mssim_task_stack_outputs(mssim_handle h, const mssim_stack_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
-  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
-  const int rows[5] = {task->tcp_row, task->cubeA_row, task->cubeB_row, task->finger1_row, task->finger2_row};
-  for (int r : rows)
-    if (r < 0 || r >= R) { h->err = "task_stack_outputs: body row out of range"; return 1; }
-  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
-  if (h->M.n_dof < 2 || !(task->gripper_width > 0.f)) { h->err = "task_stack_outputs: needs two finger joints and a gripper width > 0"; return 3; }
-  { int rc = finger_pair_list(h, task->cubeA_row, task->finger1_row, task->finger2_row); if (rc) return rc; }
-  {
-    DevState S = h->S;
-    S.tail_task.stack = *task; S.tail_pairs = h->d_pick_pairs; S.tail_npairs = h->n_pick_pairs;
-    S.tail_obs = obs; S.tail_reward = reward; S.tail_flags = flags; S.tail_head = nullptr;
-    if (control_step_with_task<4>(h, S, (hipStream_t)stream)) { HIPCHK(h, hipGetLastError()); return 0; }
-  }
-  if (h->deferred_action) { const unsigned w = take_deferred_fetch(h); flush_deferred(h, (hipStream_t)stream); h->deferred_fetch = w; }
-  if (const unsigned what = take_deferred_fetch(h))
-    hipLaunchKernelGGL(k_task_stack<true>, env_grid(h->N, 64), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
-  else
-    hipLaunchKernelGGL(k_task_stack<false>, env_grid(h->N, 64), dim3(64), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-
-int mssim_task_pusht_outputs(mssim_handle h, const mssim_pusht_task* task, float* obs, float* reward, uint8_t* flags, float* intersection, void* stream) {
-  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
-  const int rows[3] = {task->tcp_row, task->tee_row, task->goal_row};
-  for (int r : rows)
-    if (r < 0 || r >= R) { h->err = "task_pusht_outputs: body row out of range"; return 1; }
-  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
-  if (!task->consts || !(task->reward_div > 0.f)) { h->err = "task_pusht_outputs: needs the constants block and a reward divisor > 0"; return 3; }
-  {
-    DevState S = h->S;
-    S.tail_task.pusht = *task; S.tail_pairs = nullptr; S.tail_npairs = 0;
-    S.tail_obs = obs; S.tail_reward = reward; S.tail_flags = flags; S.tail_head = intersection;
-    if (control_step_with_task<5>(h, S, (hipStream_t)stream)) { HIPCHK(h, hipGetLastError()); return 0; }
-  }
-  if (h->deferred_action) { const unsigned w = take_deferred_fetch(h); flush_deferred(h, (hipStream_t)stream); h->deferred_fetch = w; }
-  // 16 lanes per env: 16 envs per block of 256
-  const unsigned what = take_deferred_fetch(h);
-  if (what) hipLaunchKernelGGL(k_task_pusht<true>, env_grid(h->N, 16), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, obs, reward, flags, intersection);
-  else hipLaunchKernelGGL(k_task_pusht<false>, env_grid(h->N, 16), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, obs, reward, flags, intersection);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-
-int64_t mssim_tail_step_count(mssim_handle h) { return h ? h->n_tail_steps : -1; }
-
 int mssim_task_pick_outputs(mssim_handle h, const mssim_pick_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
-  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
-  const int rows[5] = {task->tcp_row, task->obj_row, task->goal_row, task->finger1_row, task->finger2_row};
-  for (int r : rows)
-    if (r < 0 || r >= R) { h->err = "task_pick_outputs: body row out of range"; return 1; }
-  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
-  { int rc = finger_pair_list(h, task->obj_row, task->finger1_row, task->finger2_row); if (rc) return rc; }
-  {
-    DevState S = h->S;
-    S.tail_task.pick = *task; S.tail_pairs = h->d_pick_pairs; S.tail_npairs = h->n_pick_pairs;
-    S.tail_obs = obs; S.tail_reward = reward; S.tail_flags = flags; S.tail_head = nullptr;
-    if (control_step_with_task<1>(h, S, (hipStream_t)stream)) { HIPCHK(h, hipGetLastError()); return 0; }
-  }
-  if (h->deferred_action) { const unsigned w = take_deferred_fetch(h); flush_deferred(h, (hipStream_t)stream); h->deferred_fetch = w; }
-  if (const unsigned what = take_deferred_fetch(h))
-    hipLaunchKernelGGL(k_task_pick<true>, env_grid(h->N, 64), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
-  else
-    hipLaunchKernelGGL(k_task_pick<false>, env_grid(h->N, 64), dim3(64), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, h->d_pick_pairs, h->n_pick_pairs, obs, reward, flags);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  const int rows[] = {task->tcp_row, task->obj_row, task->goal_row, task->finger1_row, task->finger2_row};
+  const int pair_rows[] = {task->obj_row, task->finger1_row, task->finger2_row};
+  const TaskCall call{mssim_dispatch::kPick, "pick", /*refused=*/nullptr, pair_rows, obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, &TailTask::pick, task, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    hipLaunchKernelGGL(k_task_pick<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags);
+  });
 }
 
 int mssim_task_push_outputs(mssim_handle h, const mssim_push_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
-  const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
-  const int rows[3] = {task->tcp_row, task->obj_row, task->goal_row};
-  for (int r : rows)
-    if (r < 0 || r >= R) { h->err = "task_push_outputs: body row out of range"; return 1; }
-  if (!h->buf.rigid_body_data || !h->buf.art_qpos || !h->buf.art_qvel) { h->err = "buffers not bound"; return 2; }
-  {
-    DevState S = h->S;
-    S.tail_task.push = *task; S.tail_pairs = nullptr; S.tail_npairs = 0;
-    S.tail_obs = obs; S.tail_reward = reward; S.tail_flags = flags; S.tail_head = nullptr;
-    if (control_step_with_task<2>(h, S, (hipStream_t)stream)) { HIPCHK(h, hipGetLastError()); return 0; }
-  }
-  if (h->deferred_action) { const unsigned w = take_deferred_fetch(h); flush_deferred(h, (hipStream_t)stream); h->deferred_fetch = w; }
-  if (const unsigned what = take_deferred_fetch(h))
-    hipLaunchKernelGGL(k_task_push<true>, env_grid(h->N, 64), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, what, *task, obs, reward, flags);
-  else
-    hipLaunchKernelGGL(k_task_push<false>, env_grid(h->N, 256), dim3(256), 0, (hipStream_t)stream, h->M, h->S, h->buf, 0u, *task, obs, reward, flags);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  const int rows[] = {task->tcp_row, task->obj_row, task->goal_row};
+  const TaskCall call{mssim_dispatch::kPush, "push", /*refused=*/nullptr, /*pair_rows=*/nullptr, obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, &TailTask::push, task, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    // (no copy-out: an env per lane, 256 envs per block)
+    hipLaunchKernelGGL(k_task_push<decltype(fetch)::value>, env_grid(h->N, fetch ? 64 : 256), dim3(256), 0, st,
+                       h->M, h->S, h->buf, what, *task, obs, reward, flags);
+  });
 }
+
+int mssim_task_peg_outputs(mssim_handle h, const mssim_peg_task* task, float* obs, float* reward, uint8_t* flags, float* head_at_hole, void* stream) {
+  const int rows[] = {task->tcp_row, task->peg_row, task->box_row, task->finger1_row, task->finger2_row};
+  const int pair_rows[] = {task->peg_row, task->finger1_row, task->finger2_row};
+  const bool ok = task->peg_half_sizes && task->box_hole_offsets && task->box_hole_radii && head_at_hole;
+  const TaskCall call{mssim_dispatch::kPeg, "peg", ok ? nullptr : "task_peg_outputs: missing per-env geometry / output", pair_rows,
+                      obs, reward, flags, head_at_hole};
+  return task_outputs(h, call, &TailTask::peg, task, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    hipLaunchKernelGGL(k_task_peg<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, head_at_hole);
+  });
+}
+
+int mssim_task_stack_outputs(mssim_handle h, const mssim_stack_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
+  const int rows[] = {task->tcp_row, task->cubeA_row, task->cubeB_row, task->finger1_row, task->finger2_row};
+  const int pair_rows[] = {task->cubeA_row, task->finger1_row, task->finger2_row};
+  const bool ok = h->M.n_dof >= 2 && task->gripper_width > 0.f;
+  const TaskCall call{mssim_dispatch::kStack, "stack", ok ? nullptr : "task_stack_outputs: needs two finger joints and a gripper width > 0", pair_rows,
+                      obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, &TailTask::stack, task, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    hipLaunchKernelGGL(k_task_stack<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags);
+  });
+}
+
+int mssim_task_pusht_outputs(mssim_handle h, const mssim_pusht_task* task, float* obs, float* reward, uint8_t* flags, float* intersection, void* stream) {
+  const int rows[] = {task->tcp_row, task->tee_row, task->goal_row};
+  const bool ok = task->consts && task->reward_div > 0.f;
+  const TaskCall call{mssim_dispatch::kPushT, "pusht", ok ? nullptr : "task_pusht_outputs: needs the constants block and a reward divisor > 0", /*pair_rows=*/nullptr,
+                      obs, reward, flags, intersection};
+  return task_outputs(h, call, &TailTask::pusht, task, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    // 16 lanes per env: 16 envs per block of 256
+    hipLaunchKernelGGL(k_task_pusht<decltype(fetch)::value>, env_grid(h->N, 16), dim3(256), 0, st,
+                       h->M, h->S, h->buf, what, *task, obs, reward, flags, intersection);
+  });
+}
+
+int64_t mssim_tail_step_count(mssim_handle h) { return h ? h->n_tail_steps : -1; }
 
 static int make_query(mssim_handle h, const int32_t* data, int count_ints, int nq, int kind, int32_t* qid) {
   HIPCHK(h, hipSetDevice(h->device));
@@ -1621,7 +1562,7 @@ int mssim_create_pair_query(mssim_handle h, const int32_t* body_pairs, int32_t n
 int mssim_create_body_query(mssim_handle h, const int32_t* rows, int32_t n, int32_t* qid) { return make_query(h, rows, n, n, 1, qid); }
 
 static int run_query(mssim_handle h, int32_t qid, int kind, float* out, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   if (qid < 0 || qid >= (int)h->queries.size() || h->query_kind[qid] != kind) { h->err = "bad query id"; return 1; }
   int nq = h->query_n[qid];
   if (nq == 0) return 0;
@@ -1633,7 +1574,7 @@ int mssim_query_pair_impulses(mssim_handle h, int32_t qid, float* out, void* str
 int mssim_query_body_impulses(mssim_handle h, int32_t qid, float* out, void* stream) { return run_query(h, qid, 1, out, stream); }
 
 int mssim_read_internal(mssim_handle h, const char* name, float* out, int32_t max_items, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   std::string s(name);
   const size_t N = (size_t)h->N;
   const float* src = nullptr;
@@ -1665,7 +1606,7 @@ int mssim_read_internal(mssim_handle h, const char* name, float* out, int32_t ma
 }
 
 int mssim_overflow_count(mssim_handle h, void* stream) {
-  flush_deferred(h, (hipStream_t)stream);
+  settle(h, (hipStream_t)stream);
   std::vector<int> host(h->N);
   hipStream_t st = (hipStream_t)stream;
   if (hipStreamSynchronize(st) != hipSuccess) return -1;

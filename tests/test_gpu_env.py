@@ -240,6 +240,91 @@ def test_owed_calls_equal_separate_calls():
                 assert torch.equal(x, y), (mode, step, k, (x.float() - y.float()).abs().max())
 
 
+def _owed_rollout(settle, N=17, seed=13, control_mode=None):
+    """PickCube, N envs (17: one block of 16 envs and one env more, a partial block and a partial wave), 3 control steps after
+    the first. Every step is owed (step_action + fetch deferred), `settle(base, px, task, obs, rew, fl)` comes next, then
+    task_pick_outputs (unless `settle` returns True); `settle` None: the separate calls apply_action / step / fetch. -> per step the outputs and buffers"""
+    import gymnasium as gym
+
+    g = torch.Generator().manual_seed(seed)
+    adim = 4 if control_mode == "pd_ee_delta_pos" else 8
+    acts = [(2 * torch.rand(N, adim, generator=g) - 1).cuda() for _ in range(4)]
+    env = gym.make("PickCube-v1", num_envs=N, sim_backend="physx_cuda", **(dict(control_mode=control_mode) if control_mode else {}))
+    base = env.unwrapped
+    env.reset(seed=9)
+    env.step(acts[0])  # sets the action map, builds the task struct
+    px, task = base.scene.px, base._fused_state["task"]
+    out = []
+    for a in acts[1:]:
+        obs = torch.empty((N, 42), device="cuda"); rew = torch.empty(N, device="cuda"); fl = torch.empty((N, 4), dtype=torch.uint8, device="cuda")
+        es = torch.empty_like(base._elapsed_steps)
+        task.elapsed_steps, task.elapsed_out = base._elapsed_steps.data_ptr(), es.data_ptr()
+        if settle is None:
+            px.apply_action(a); px.step(5); px.gpu_fetch_all()
+        else:
+            px.step_action(a, 5, defer=True); px.defer_fetch_all()
+        if settle is None or settle(base, px, task, obs, rew, fl) is not True:  # (True: it has run the epilogue itself)
+            px.task_pick_outputs(task, obs, rew, fl)
+        base._elapsed_steps.copy_(es)
+        out.append([t.cpu().clone() for t in (obs, rew, fl, px.cuda_rigid_body_data.torch(), px.cuda_articulation_qpos.torch(),
+                                               px.cuda_articulation_target_qpos.torch(), px.cuda_articulation_qacc.torch())])
+    env.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def owed_reference():
+    return _owed_rollout(None)
+
+
+def _settle_by_rejected_call(base, px, task, obs, rew, fl):
+    """a call the library turns down (rc 1) performs nothing: the owed step and fetch stay owed, and the correct call that
+    follows still runs them and the epilogue as one launch"""
+    from maniskill_amd.native import NativeError
+
+    bad = type(task).from_buffer_copy(task)
+    bad.tcp_row = -1
+    t0 = px.tail_step_count()
+    with pytest.raises(NativeError, match=r"\(1\): task_pick_outputs: body row out of range"):
+        px.task_pick_outputs(bad, obs, rew, fl)
+    assert px.tail_step_count() == t0
+    px.task_pick_outputs(task, obs, rew, fl)
+    assert px.tail_step_count() == t0 + 1, "the call after the rejected one did not take the fused tail"
+    return True
+
+
+OWED_SETTLERS = {
+    "set_timestep": lambda base, px, *_: px._sim.set_timestep(px._sim.get_timestep()),
+    "set_drive_properties": lambda base, px, *_: px.set_drive_properties(px.model.arrays["dof_drive"]),
+    "read_internal": lambda base, px, *_: px.read_internal("q", 9),
+    "link_jacobian": lambda base, px, *_: px.link_jacobian(px.model.link_names.index("panda_hand_tcp")),
+    "overflow_count": lambda base, px, *_: px.overflow_count(),
+    "rejected_call_first": _settle_by_rejected_call,
+}
+
+
+@pytest.mark.parametrize("mode", list(OWED_SETTLERS))
+def test_owed_calls_settled_by_other_entry_points_equal_separate_calls(owed_reference, mode):
+    """as test_owed_calls_equal_separate_calls, the owed step and fetch performed by other entry points of include/mssim.h
+    (each settles what is owed before it does its own work), and by the call after a rejected one: bit-identical to the
+    separate calls"""
+    got = _owed_rollout(OWED_SETTLERS[mode])
+    for step, (r, o) in enumerate(zip(owed_reference, got)):
+        for k, (x, y) in enumerate(zip(r, o)):
+            assert torch.equal(x, y), (mode, step, k, (x.float() - y.float()).abs().max())
+
+
+def test_owed_step_under_an_end_effector_map_is_settled_before_the_owed_fetch():
+    """pd_ee_delta_pos: the action map has an end-effector block, so an owed step is apply_action + step and never the fused
+    tail. Settled by an entry point that is no task epilogue (read_internal), the owed copy-out must come after that step:
+    buffers and outputs bit-identical to the separate calls apply_action / step / fetch"""
+    ref = _owed_rollout(None, control_mode="pd_ee_delta_pos")
+    got = _owed_rollout(OWED_SETTLERS["read_internal"], control_mode="pd_ee_delta_pos")
+    for step, (r, o) in enumerate(zip(ref, got)):
+        for k, (x, y) in enumerate(zip(r, o)):
+            assert torch.equal(x, y), (step, k, (x.float() - y.float()).abs().max())
+
+
 @pytest.mark.parametrize("env_id", ["PickCube-v1", "PushCube-v1"])
 def test_full_size_run_equals_small_run_env_by_env(env_id):
     """size-independent property at BASELINE's full size: envs never interact, so the first 64 envs of a
