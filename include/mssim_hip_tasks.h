@@ -1,4 +1,5 @@
-/* mssim_hip_tasks.h -- task epilogues of the HIP library only (libmssim.so), outside the core ABI of mssim.h.
+/* mssim_hip_tasks.h -- extras of the HIP library only (libmssim.so), outside the core ABI of mssim.h: task epilogues
+ * and the iterative-IK block of the action map.
  *
  * mssim.h is the contract both implementations export (the HIP library and the CPU oracle, every MSSIM_FN of it under
  * its own prefix). The entry points below exist in the HIP library alone: plain extern "C" symbols, bound by
@@ -75,6 +76,34 @@ int mssim_task_pusht_outputs(mssim_handle h, const mssim_pusht_task* task, float
  * tail (a deferred step_action + fetch consumed by a task_*_outputs call), against the separate epilogue launch.
  * A host counter: no sync. */
 int64_t mssim_tail_step_count(mssim_handle h);
+
+/* Iterative-IK block of the action map: the end-effector modes that track a target pose (pd_ee_pose,
+ * pd_ee_target_delta_pos, pd_ee_target_delta_pose; agents/controllers/pd_ee_pose.py). With the block set, apply_action,
+ * step_action and defer_step_action clip and scale its columns as the block of set_ee_action_map does, update
+ * `target_pose` in place
+ *     mode 0: p = lin, q = euler_xyz(rot) (identity with 3 rows)
+ *     mode 1: p = p_prev + lin, q = euler_xyz(rot) * q_prev (q_prev with 3 rows); no renormalisation
+ * and solve, per env, a damped-least-squares IK of link `link_index` for that pose in the articulation's ROOT frame
+ * over the joints on the link's path, from the visible qpos buffer:
+ *     repeat at most max_iters: err = target - FK(q) (6 rows: + rotation vector of q_t * conj(q_e));
+ *       stop when max|err| < tolerance; step = J^T (J J^T + damping I)^-1 err, scaled so that max|step| <= max_step;
+ *       q = clip(q + step, joint limits)
+ * The exit is per env: an env's answer does not depend on the batch it is in. The result becomes the position target
+ * (visible buffer and simulation state) of the path dofs, which must all be flagged 4 in set_action_map (call it
+ * first) and number at most 8. A NaN in an env's columns or target gives NaN targets and a NaN target pose for that
+ * env alone. The block runs as one launch after the joint-space map, followed by the step. Setting this block
+ * removes the one of set_ee_action_map and the other way round. */
+typedef struct mssim_ee_ik_map {
+  int32_t link_index;     /* < 0 removes the block */
+  int32_t column0, rows;  /* 3: position, 6: position + XYZ Euler angles */
+  int32_t mode;           /* 0 absolute (pd_ee_pose): target = action; 1 target-delta: target = compose(previous target, action) */
+  float low, high, rot_scale; int32_t flags;   /* as set_ee_action_map: flags & 2 = clip and map / clip by norm and scale */
+  int32_t max_iters; float damping, max_step, tolerance;   /* 60, 1e-3, 0.3, 1e-5; tolerance 0 = run exactly max_iters */
+} mssim_ee_ik_map;
+int mssim_set_ee_ik_map(mssim_handle h, const mssim_ee_ik_map* map, float* target_pose /* device [N][7] p, q(wxyz): read and written in place by every apply */);
+/* The solve alone, with the chain and settings of the block set last: q_out = q0 with the path dofs solved. */
+int mssim_ee_ik_solve(mssim_handle h, const float* target_pose /* [N][7] */, const float* q0 /* [N][n_dof] or NULL = visible qpos */,
+                      float* q_out /* [N][n_dof]; dofs off the path copied from q0 */, int32_t* iters_out /* optional [N] */, void* stream);
 
 #ifdef __cplusplus
 }

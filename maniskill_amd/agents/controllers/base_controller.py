@@ -189,26 +189,39 @@ class CombinedController(DictController):
 
     def fused_action_spec(self):
         """per-dof (column, low, high, flags) arrays for `px.set_action_map`, or None if any
-        sub-controller cannot be expressed as an affine action -> target map"""
+        sub-controller cannot be expressed as an affine action -> target map. Fifth element: the end-effector block of
+        `px.set_ee_action_map` or None. With an iterative-IK block (`px.set_ee_ik_map`) there is a sixth element,
+        (link index, first action column, rows, mode, low, high, rot_scale, flags); its state tensor is
+        `fused_ik_target()`."""
         n = self.articulation.max_dof
         col, lo, hi, fl = [-1] * n, [0.0] * n, [0.0] * n, [0] * n
         ee = None  # end-effector block: (link index, first action column, rows, low, high, rot_scale, flags)
+        ik, self._fused_ik_controller = None, None
         for uid, c in self.controllers.items():
             spec = getattr(c, "fused_action_spec", lambda: None)()
             if spec is None:
                 return None
             start, _ = self.action_mapping[uid]
             if isinstance(spec, dict):
-                if ee is not None:
+                if ee is not None or ik is not None:
                     return None  # one end-effector block
-                link, rows, l, h, rs, f = spec["ee"]
-                ee = (link, start, rows, l, h, rs, f)
+                if "ik" in spec:
+                    link, rows, mode, l, h, rs, f = spec["ik"]
+                    ik, self._fused_ik_controller = (link, start, rows, mode, l, h, rs, f), c
+                else:
+                    link, rows, l, h, rs, f = spec["ee"]
+                    ee = (link, start, rows, l, h, rs, f)
                 for dof in spec["dofs"]:
                     fl[dof] = 4  # driven by the end-effector block
                 continue
             for dof, lcol, l, h, f in spec:
                 col[dof], lo[dof], hi[dof], fl[dof] = start + lcol, l, h, f
-        return col, lo, hi, fl, ee
+        return (col, lo, hi, fl, ee) if ik is None else (col, lo, hi, fl, ee, ik)
+
+    def fused_ik_target(self):
+        """state tensor of the iterative-IK block of the last `fused_action_spec()`, or None without one"""
+        c = getattr(self, "_fused_ik_controller", None)
+        return None if c is None else c.fused_ik_target()
 
     def to_action_dict(self, action):
         return {uid: action[s:e] for uid, (s, e) in self.action_mapping.items()}

@@ -44,19 +44,29 @@ class PDEEPosController(PDJointPosController):
         """the delta controllers (`pd_ee_delta_pos`, `pd_ee_delta_pose`) are one pseudo-inverse step of the
         commanded translation (and rotation vector): the native action map has an end-effector block for
         exactly that (include/mssim.h `set_ee_action_map`). Returns {"ee": (link index, rows, low, high,
-        rot_scale, flags), "dofs": [...]}; every other configuration keeps IK in torch between the action and
-        the joint targets."""
+        rot_scale, flags), "dofs": [...]}.
+        The modes that track a target pose (`pd_ee_target_delta_pos`, `pd_ee_target_delta_pose`: use_target with
+        use_delta; `pd_ee_pose`: the absolute pose) have the iterative-IK block (include/mssim_hip_tasks.h
+        `set_ee_ik_map`): {"ik": (link index, rows, mode, low, high, rot_scale, flags), "dofs": [...]}, mode 0 absolute,
+        1 target-delta; its state is `fused_ik_target()`. Every other configuration keeps IK in torch between the
+        action and the joint targets."""
         cfg = self.config
         pose = type(cfg) is PDEEPoseControllerConfig
-        if not (pose or type(cfg) is PDEEPosControllerConfig) or not cfg.use_delta or cfg.use_target or cfg.interpolate:
+        if not (pose or type(cfg) is PDEEPosControllerConfig) or cfg.interpolate:
+            return None
+        tracked = cfg.use_target if cfg.use_delta else pose  # solved iteratively for a target pose the controller keeps
+        if not cfg.use_delta and not pose:
             return None
         if cfg.frame != ("root_translation:root_aligned_body_rotation" if pose else "root_translation"):
             return None
-        lo, hi = np.broadcast_to(cfg.pos_lower, 3), np.broadcast_to(cfg.pos_upper, 3)
+        if not self._normalize_action:
+            lo = hi = np.zeros(3)  # (raw columns: the bounds are not read)
+        else:
+            lo, hi = np.broadcast_to(cfg.pos_lower, 3), np.broadcast_to(cfg.pos_upper, 3)
         if self._normalize_action and not (np.all(lo == lo[0]) and np.all(hi == hi[0])):
             return None  # the native block takes one [low, high] for the three axes
         rot_scale = 0.0
-        if pose:
+        if pose and self._normalize_action:
             rl = np.broadcast_to(cfg.rot_lower, 3)
             if not np.all(rl == rl[0]):
                 return None
@@ -64,8 +74,21 @@ class PDEEPosController(PDJointPosController):
         if set(self.kinematics.active_ancestor_joint_idxs) != set(int(i) for i in self.active_joint_indices.tolist()):
             return None  # the step moves every joint on the link's path: they must all be this controller's
         flags = 2 if self._normalize_action else 0
+        dofs = [int(i) for i in self.active_joint_indices.tolist()]
+        if tracked:
+            if len(dofs) > 8:
+                return None  # the iterative-IK kernel keeps a chain of at most 8 joints in registers
+            return dict(ik=(self.kinematics.end_link_idx, 6 if pose else 3, 1 if cfg.use_delta else 0, float(lo[0]), float(hi[0]), rot_scale, flags), dofs=dofs)
         return dict(ee=(self.kinematics.end_link_idx, 6 if pose else 3, float(lo[0]), float(hi[0]), rot_scale, flags),
-                    dofs=[int(i) for i in self.active_joint_indices.tolist()])
+                    dofs=dofs)
+
+    def fused_ik_target(self):
+        """the [N, 7] float32 target pose (root frame) that the iterative-IK block reads and updates in place: the very
+        tensor behind `_target_pose`, so reset / get_state / set_state see what the torch path would show them"""
+        raw, N = self._target_pose.raw_pose, self.scene.num_envs
+        if raw.dtype != torch.float32 or tuple(raw.shape) != (N, 7) or not raw.is_contiguous():
+            self._target_pose = Pose.create(raw.to(torch.float32).expand(N, 7).contiguous())
+        return self._target_pose.raw_pose
 
     # ---- where the end effector is --------------------------------------------------------------------
     @property
@@ -87,6 +110,8 @@ class PDEEPosController(PDJointPosController):
         if self._target_pose is not None and not self.scene._reset_mask_all:
             rows = self.scene._reset_idx
             self._target_pose.raw_pose[rows] = here[rows]
+        elif self._target_pose is not None and self._target_pose.raw_pose.shape == here.shape and self._target_pose.raw_pose.dtype == here.dtype:
+            self._target_pose.raw_pose.copy_(here)  # (a persistent buffer: the native IK block holds its address)
         else:
             self._target_pose = Pose.create(here.clone())
 
@@ -130,7 +155,7 @@ class PDEEPosController(PDJointPosController):
     def get_state(self) -> dict:
         if not self.config.use_target:
             return {}
-        return dict(target_pose=self._target_pose.raw_pose)
+        return dict(target_pose=self._target_pose.raw_pose.clone())  # (the buffer itself is updated in place by the native IK block)
 
     def set_state(self, state: dict):
         if not self.config.use_target:

@@ -518,6 +518,8 @@ __global__ void k_apply_action(DevModel M, DevState S, mssim_buffers B, const fl
   }
 }
 
+#include "mssim_ik.h"  // iterative IK block of the action map (the end-effector modes that track a target pose)
+
 // PickCube-style evaluate / obs / reward
 // FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
 MS_DEV void task_pick_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_pick_task& T, const int* __restrict__ pairs, int npairs,
@@ -1006,6 +1008,8 @@ struct mssim_sim {
   std::string err;
   int* d_act_col = nullptr; float* d_act_lo = nullptr; float* d_act_hi = nullptr; int* d_act_flags = nullptr;
   EeMap ee{-1, 0, 3, 0.f, 0.f, 0.f, 0};
+  IkChain ik = [] { IkChain c{}; c.link = -1; return c; }();  // iterative-IK block (mssim_set_ee_ik_map); excludes `ee`
+  float* ik_target_pose = nullptr;                            // the caller's [N][7] state of that block
   int act_max_col = -1;  // highest action column the joint map reads
   // profiling (bench roofline block): event pairs recorded on the launch stream
   bool profiling = false;
@@ -1298,7 +1302,7 @@ static DevState state_with_action(mssim_handle h, const float* action, int actio
 // every column the maps read must exist: the kernels index action[env * action_dim + column] unchecked
 static int check_action_dim(mssim_handle h, int32_t action_dim) {
   if (!h->d_act_col) { h->err = "set_action_map has not been called"; return 1; }
-  const int need = std::max(h->act_max_col + 1, h->ee.link >= 0 ? h->ee.col0 + h->ee.rows : 0);
+  const int need = std::max({h->act_max_col + 1, h->ee.link >= 0 ? h->ee.col0 + h->ee.rows : 0, h->ik.link >= 0 ? h->ik.col0 + h->ik.rows : 0});
   if (action_dim < need) {
     h->err = "action has " + std::to_string(action_dim) + " columns, the action map reads " + std::to_string(need);
     return 2;
@@ -1308,9 +1312,13 @@ static int check_action_dim(mssim_handle h, int32_t action_dim) {
 static void launch_apply_action(mssim_handle h, const float* action, int action_dim, hipStream_t st) {
   hipLaunchKernelGGL(k_apply_action, env_grid(h->N, 256), dim3(256), 0, st, h->M, h->S, h->buf, action, action_dim,
                      h->d_act_col, h->d_act_lo, h->d_act_hi, h->d_act_flags, h->ee);
+  if (h->ik.link >= 0) {  // the joint-space rows are written; the iterative-IK block follows in a launch of its own
+    const IkIo io{action, action_dim, h->d_act_flags, h->ik_target_pose, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(h->ik.rows == 6 ? k_ee_ik<6> : k_ee_ik<3>, env_grid(h->N, 64), dim3(64), 0, st, h->ik, h->S, h->buf, h->M.n_dof, io);
+  }
 }
 static int step_action_now(mssim_handle h, const float* action, int32_t action_dim, int32_t n_substeps, hipStream_t st) {
-  if (n_substeps <= 0 || h->ee.link >= 0) {  // end-effector block: apply_action, then step
+  if (n_substeps <= 0 || h->ee.link >= 0 || h->ik.link >= 0) {  // end-effector block: apply_action, then step
     launch_apply_action(h, action, action_dim, st);
     return step_now(h, h->S, n_substeps, st);
   }
@@ -1407,6 +1415,78 @@ int mssim_set_ee_action_map(mssim_handle h, int32_t link_index, int32_t column0,
   settle(h, h->owed.stream);
   if (link_index >= h->M.n_link || (link_index >= 0 && rows != 3 && rows != 6)) { h->err = "set_ee_action_map: bad link index / rows"; return 1; }
   h->ee = EeMap{link_index < 0 ? -1 : (int)link_index, (int)column0, (int)rows, low, high, rot_scale, (int)flags};
+  if (link_index >= 0) h->ik.link = -1;  // the two end-effector blocks exclude each other
+  return 0;
+}
+
+// a small constant table of the model back on the host (set-time only)
+extern "C++" {
+template <typename Tt>
+static int download(mssim_handle h, const Tt* src, size_t count, std::vector<Tt>* dst) {
+  dst->resize(count);
+  if (count > 0) HIPCHK(h, hipMemcpy(dst->data(), src, count * sizeof(Tt), hipMemcpyDeviceToHost));
+  return 0;
+}
+}
+
+int mssim_set_ee_ik_map(mssim_handle h, const mssim_ee_ik_map* map, float* target_pose) {
+  settle(h, h->owed.stream);
+  if (!map) { h->err = "set_ee_ik_map: no map"; return 1; }
+  if (map->link_index < 0) { h->ik.link = -1; h->ik_target_pose = nullptr; return 0; }
+  const DevModel& M = h->M;
+  if (map->link_index >= M.n_link || (map->rows != 3 && map->rows != 6) || (map->mode != 0 && map->mode != 1) || map->column0 < 0 || map->max_iters < 0) {
+    h->err = "set_ee_ik_map: bad link index / rows / mode / column / iteration count"; return 1;
+  }
+  if (!target_pose) { h->err = "set_ee_ik_map: no target_pose buffer"; return 1; }
+  if (!h->d_act_flags) { h->err = "set_ee_ik_map: set_action_map has not been called"; return 1; }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<int> parent, type, link_body, flags;
+  std::vector<float> frame, axis, limit, link_frame;
+  int rc;
+  if ((rc = download(h, M.dof_parent, (size_t)M.n_dof, &parent)) || (rc = download(h, M.dof_type, (size_t)M.n_dof, &type)) ||
+      (rc = download(h, M.link_body, (size_t)M.n_link, &link_body)) || (rc = download(h, (const int*)h->d_act_flags, (size_t)M.n_dof, &flags)) ||
+      (rc = download(h, M.dof_frame, (size_t)7 * M.n_dof, &frame)) || (rc = download(h, M.dof_axis, (size_t)3 * M.n_dof, &axis)) ||
+      (rc = download(h, M.dof_limit, (size_t)2 * M.n_dof, &limit)) || (rc = download(h, M.link_frame, (size_t)7 * M.n_link, &link_frame)))
+    return rc;
+  std::vector<int> path;
+  for (int b = link_body[map->link_index]; b >= 0; b = parent[b]) path.insert(path.begin(), b);
+  if (path.empty()) { h->err = "set_ee_ik_map: the link has no joint on its path"; return 1; }
+  if ((int)path.size() > MSSIM_IK_MAX_JOINTS) {
+    h->err = "set_ee_ik_map: the link has " + std::to_string(path.size()) + " joints on its path, the iterative IK takes at most " + std::to_string(MSSIM_IK_MAX_JOINTS);
+    return 1;
+  }
+  for (int j : path)
+    if (!(flags[j] & 4)) { h->err = "set_ee_ik_map: dof " + std::to_string(j) + " is on the link's path but not flagged 4 in the joint map"; return 1; }
+  auto unit7 = [](const float* src, float* dst) {  // the quaternion normalised in double, as the reference does
+    const double w = src[3], x = src[4], y = src[5], z = src[6], n = std::sqrt(w * w + x * x + y * y + z * z);
+    for (int c = 0; c < 3; c++) dst[c] = src[c];
+    dst[3] = (float)(w / n); dst[4] = (float)(x / n); dst[5] = (float)(y / n); dst[6] = (float)(z / n);
+  };
+  IkChain c{};
+  c.link = map->link_index; c.n = (int)path.size(); c.rows = map->rows; c.col0 = map->column0; c.mode = map->mode; c.flags = map->flags;
+  c.lo = map->low; c.hi = map->high; c.rot_scale = map->rot_scale;
+  c.max_iters = map->max_iters; c.damping = map->damping; c.max_step = map->max_step; c.tol = map->tolerance;
+  for (int k = 0; k < c.n; k++) {
+    const int j = path[k];
+    c.dof[k] = j; c.revolute[k] = type[j] == MSSIM_JOINT_REVOLUTE;
+    unit7(&frame[7 * (size_t)j], c.frame[k]);
+    for (int a = 0; a < 3; a++) c.axis[k][a] = axis[3 * (size_t)j + a];
+    c.lower[k] = limit[2 * (size_t)j]; c.upper[k] = limit[2 * (size_t)j + 1];
+  }
+  unit7(&link_frame[7 * (size_t)map->link_index], c.tip);
+  h->ik = c;
+  h->ik_target_pose = target_pose;
+  h->ee.link = -1;  // the two end-effector blocks exclude each other
+  return 0;
+}
+
+int mssim_ee_ik_solve(mssim_handle h, const float* target_pose, const float* q0, float* q_out, int32_t* iters_out, void* stream) {
+  settle(h, (hipStream_t)stream);
+  if (h->ik.link < 0) { h->err = "ee_ik_solve: set_ee_ik_map has not been called"; return 1; }
+  if (!target_pose || !q_out) { h->err = "ee_ik_solve: no target_pose / q_out"; return 1; }
+  const IkIo io{nullptr, 0, nullptr, const_cast<float*>(target_pose), q0, q_out, iters_out};  // (read only in this form)
+  hipLaunchKernelGGL(h->ik.rows == 6 ? k_ee_ik<6> : k_ee_ik<3>, env_grid(h->N, 64), dim3(64), 0, (hipStream_t)stream, h->ik, h->S, h->buf, h->M.n_dof, io);
+  HIPCHK(h, hipGetLastError());
   return 0;
 }
 
@@ -1464,7 +1544,7 @@ static int task_outputs(mssim_handle h, const TaskCall& c, Task TailTask::*slot,
   if (c.pair_rows)
     if (int rc = finger_pair_list(h, c.pair_rows[0], c.pair_rows[1], c.pair_rows[2])) return rc;
   const Owed& o = h->owed;
-  if (h->tail_fn[c.id] && o.action && o.fetch && o.nsub > 0 && st == o.stream && h->ee.link < 0) {
+  if (h->tail_fn[c.id] && o.action && o.fetch && o.nsub > 0 && st == o.stream && h->ee.link < 0 && h->ik.link < 0) {
     DevState S = state_with_action(h, o.action, o.adim);
     S.tail_task.*slot = *task;
     S.tail_pairs = c.pair_rows ? h->d_finger_pairs : nullptr; S.tail_npairs = c.pair_rows ? h->n_finger_pairs : 0;

@@ -560,9 +560,20 @@ class BaseEnv(gym.Env):
         if self._fused_action_key != key:
             spec = getattr(ctrl, "fused_action_spec", lambda: None)()
             self._fused_action_key, self._fused_action_ok = key, spec is not None
+            self._fused_ik = spec[5] if spec is not None and len(spec) > 5 else None
+            self._fused_ik_ptr = None
             if spec is not None:
                 self.scene.px.set_action_map(*spec[:4])
                 self.scene.px.set_ee_action_map(spec[4])
+                if self._fused_ik is None:
+                    self.scene.px.set_ee_ik_map(None)  # (a mode switch away from a target-tracking mode)
+        if self._fused_action_ok and self.__dict__.get("_fused_ik") is not None:
+            # the block's state is the controller's own target-pose tensor: bound once, and again whenever the
+            # controller has replaced it (set_state, a step on the torch path)
+            pose = ctrl.fused_ik_target()
+            if pose.data_ptr() != self._fused_ik_ptr:
+                self.scene.px.set_ee_ik_map(self._fused_ik, pose)
+                self._fused_ik_ptr = pose.data_ptr()
         return self._fused_action_ok and action.is_contiguous()
 
     _fused_epilogue_next = False

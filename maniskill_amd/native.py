@@ -167,6 +167,13 @@ class PushTTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class EeIkMap(C.Structure):
+    """mssim_ee_ik_map of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("link_index", C.c_int32), ("column0", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32),
+                ("low", C.c_float), ("high", C.c_float), ("rot_scale", C.c_float), ("flags", C.c_int32),
+                ("max_iters", C.c_int32), ("damping", C.c_float), ("max_step", C.c_float), ("tolerance", C.c_float)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -228,6 +235,8 @@ class NativeLib:
             ("task_stack_outputs", C.c_int, [H, C.POINTER(StackTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_pusht_outputs", C.c_int, [H, C.POINTER(PushTTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
+            ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
+            ("ee_ik_solve", C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         ):
             if hasattr(self.lib, self.prefix + name):
                 self._fn(name, restype, argtypes)
@@ -393,6 +402,17 @@ class NativeSim:
         if self.lib.tail_step_count is None:
             raise NativeError(f"{self.lib.path} has no tail_step_count (an extra of the HIP library, include/mssim_hip_tasks.h)")
         return int(self.lib.tail_step_count(self.h))
+
+    def set_ee_ik_map(self, ik: "EeIkMap", target_pose_ptr):
+        """iterative-IK block of the action map (HIP library only); `ik.link_index < 0` removes it"""
+        if self.lib.set_ee_ik_map is None:
+            raise NativeError(f"{self.lib.path} has no set_ee_ik_map (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.set_ee_ik_map(self.h, C.byref(ik), target_pose_ptr), "set_ee_ik_map")
+
+    def ee_ik_solve(self, target_pose_ptr, q0_ptr, q_out_ptr, iters_ptr=None, stream=None):
+        if self.lib.ee_ik_solve is None:
+            raise NativeError(f"{self.lib.path} has no ee_ik_solve (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.ee_ik_solve(self.h, target_pose_ptr, q0_ptr, q_out_ptr, iters_ptr, stream), "ee_ik_solve")
 
     def task_pick_outputs(self, task: "PickTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
         self._check(self.lib.task_pick_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_pick_outputs")

@@ -319,6 +319,38 @@ class MssimSystem:
         else:
             self._sim.set_ee_action_map(*ee)
 
+    IK_DEFAULTS = dict(max_iters=60, damping=1e-3, max_step=0.3, tolerance=1e-5)  # Kinematics.compute_ik's iterative branch
+
+    def set_ee_ik_map(self, ik, target_pose: torch.Tensor = None, **settings):
+        """iterative-IK block of the action map (include/mssim_hip_tasks.h `set_ee_ik_map`; HIP library only):
+        `ik` = `(link_index, column0, rows, mode, low, high, rot_scale, flags)` or None to remove the block;
+        `target_pose` [N, 7] f32 is the block's state, read and written in place by every apply (kept alive here);
+        `settings` override IK_DEFAULTS. Call `set_action_map` first: it flags the dofs the block drives."""
+        if ik is None:
+            if self._sim.lib.set_ee_ik_map is not None:  # (a library without the block has none to remove)
+                self._sim.set_ee_ik_map(native.EeIkMap(link_index=-1), None)
+            self._ik_target_pose = None
+            return
+        assert target_pose.dtype == torch.float32 and target_pose.is_contiguous() and tuple(target_pose.shape) == (self.num_envs, 7)
+        link, column0, rows, mode, low, high, rot_scale, flags = ik
+        s = dict(self.IK_DEFAULTS, **settings)
+        m = native.EeIkMap(int(link), int(column0), int(rows), int(mode), float(low), float(high), float(rot_scale), int(flags),
+                           int(s["max_iters"]), float(s["damping"]), float(s["max_step"]), float(s["tolerance"]))
+        self._sim.set_ee_ik_map(m, target_pose.data_ptr())
+        self._ik_target_pose = target_pose
+
+    def ee_ik_solve(self, target_pose: torch.Tensor, q0: torch.Tensor = None, return_iters: bool = False):
+        """the solve of the block set last, alone: joint positions [N, n_dof] whose path dofs reach `target_pose`
+        [N, 7] (root frame), started from `q0` [N, n_dof] (None: the visible qpos); dofs off the path are copied"""
+        n = self.model.n_dof
+        assert target_pose.dtype == torch.float32 and target_pose.is_contiguous() and tuple(target_pose.shape) == (self.num_envs, 7)
+        assert q0 is None or (q0.dtype == torch.float32 and q0.is_contiguous() and tuple(q0.shape) == (self.num_envs, n))
+        out = torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device)
+        iters = torch.empty(self.num_envs, dtype=torch.int32, device=self.device) if return_iters else None
+        self._sim.ee_ik_solve(target_pose.data_ptr(), None if q0 is None else q0.data_ptr(), out.data_ptr(),
+                              None if iters is None else iters.data_ptr(), self._stream())
+        return (out, iters) if return_iters else out
+
     def apply_action(self, action: torch.Tensor):
         """affine action -> drive targets in one launch (include/mssim.h `apply_action`)"""
         assert action.dtype == torch.float32 and action.is_contiguous() and action.shape[0] == self.num_envs

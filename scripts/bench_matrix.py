@@ -7,18 +7,31 @@ import torch
 import maniskill_amd.envs  # noqa
 import gymnasium as gym
 
+def action_source(base, N, adim, control_mode):
+    """random actions in [-1, 1]; `pd_ee_pose` (absolute, raw columns) gets ONE fixed reachable pose instead: the TCP's
+    start pose in the root frame, 5 cm higher, as position + XYZ Euler angles, and a random gripper column"""
+    if control_mode != "pd_ee_pose":
+        return lambda: 2 * torch.rand(N, adim, device="cuda") - 1
+    P = base.agent.controller.controllers["arm"].ee_pose_at_base.raw_pose
+    w, x, y, z = P[:, 3], P[:, 4], P[:, 5], P[:, 6]
+    euler = torch.stack([torch.atan2(-2 * (y * z - w * x), 1 - 2 * (x * x + y * y)), torch.asin((2 * (x * z + w * y)).clamp(-1, 1)),
+                         torch.atan2(-2 * (x * y - w * z), 1 - 2 * (y * y + z * z))], 1)
+    pose = torch.cat([P[:, :3] + torch.tensor([0.0, 0.0, 0.05], device=P.device), euler], 1)
+    return lambda: torch.cat([pose, 2 * torch.rand(N, adim - 6, device="cuda") - 1], 1)
+
 def run(env_id, N, steps=1000, control_mode="pd_joint_delta_pos", **kw):
     torch.manual_seed(2022)
     env = gym.make(env_id, num_envs=N, obs_mode="state", control_mode=control_mode, **kw)
     base = env.unwrapped
     adim = base.single_action_space.shape[0]
     env.reset(seed=2022)
-    env.step(2 * torch.rand(N, adim, device="cuda") - 1)
+    act = action_source(base, N, adim, control_mode)
+    env.step(act())
     env.reset(seed=2022)
     torch.cuda.synchronize(); t = time.perf_counter()
     dt_200 = None
     for i in range(steps):
-        env.step(2 * torch.rand(N, adim, device="cuda") - 1)
+        env.step(act())
         if i == 199:
             torch.cuda.synchronize(); dt_200 = time.perf_counter() - t
     torch.cuda.synchronize(); dt_step = time.perf_counter() - t
@@ -26,7 +39,7 @@ def run(env_id, N, steps=1000, control_mode="pd_joint_delta_pos", **kw):
     env.reset(seed=2022)
     torch.cuda.synchronize(); t = time.perf_counter()
     for i in range(steps):
-        env.step(2 * torch.rand(N, adim, device="cuda") - 1)
+        env.step(act())
         if (i + 1) % 200 == 0:
             env.reset()
     torch.cuda.synchronize(); dt_reset = time.perf_counter() - t
@@ -39,6 +52,9 @@ def run(env_id, N, steps=1000, control_mode="pd_joint_delta_pos", **kw):
 only = sys.argv[1:]
 for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("PegInsertionSide-v1", 2048), {}),
                  (("PickCube-v1", 4096), dict(control_mode="pd_ee_delta_pos")), (("PickCube-v1", 4096), dict(control_mode="pd_ee_delta_pose")),
+                 # the modes that track a target pose: the iterative-IK block of the action map (MS_FUSED=0: the torch solver)
+                 (("PickCube-v1", 4096), dict(control_mode="pd_ee_target_delta_pos")), (("PickCube-v1", 4096), dict(control_mode="pd_ee_target_delta_pose")),
+                 (("PickCube-v1", 4096), dict(control_mode="pd_ee_pose")),
                  (("PickCube-v1", 16384), {}),
                  (("StackCube-v1", 4096), {}),  # two cubes: the two-row control-step kernel (MS_FUSED=0: the torch epilogue)
                  (("PushT-v1", 4096), {}),  # panda_stick + T block: k_solve16<7, 5> with the pseudo-render at its tail (MS_FUSED=0: torch)

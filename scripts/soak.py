@@ -20,11 +20,20 @@ env = gym.make(env_id, num_envs=N, obs_mode="state", control_mode=mode, **extra)
 base = env.unwrapped
 adim = base.single_action_space.shape[0]
 env.reset(seed=seed)
+if mode == "pd_ee_pose":  # absolute, raw columns: poses around the TCP's start (position + XYZ Euler angles), random gripper
+    P = base.agent.controller.controllers["arm"].ee_pose_at_base.raw_pose.clone()
+    w, x, y, z = P[:, 3], P[:, 4], P[:, 5], P[:, 6]
+    centre = torch.cat([P[:, :3], torch.stack([torch.atan2(-2 * (y * z - w * x), 1 - 2 * (x * x + y * y)), torch.asin((2 * (x * z + w * y)).clamp(-1, 1)),
+                                               torch.atan2(-2 * (x * y - w * z), 1 - 2 * (y * y + z * z))], 1)], 1)
+    spread = torch.tensor([0.1, 0.1, 0.1, 0.3, 0.3, 0.3], device="cuda")
+    action = lambda: torch.cat([centre + spread * (2 * torch.rand(N, 6, device="cuda") - 1), 2 * torch.rand(N, adim - 6, device="cuda") - 1], 1)
+else:
+    action = lambda: 2 * torch.rand(N, adim, device="cuda") - 1
 bad = torch.zeros((), dtype=torch.int64, device="cuda")
 omax = torch.zeros((), device="cuda")
 t0 = time.perf_counter()
 for i in range(1, K + 1):
-    obs, rew, term, trunc, info = env.step(2 * torch.rand(N, adim, device="cuda") - 1)
+    obs, rew, term, trunc, info = env.step(action())
     bad += (~torch.isfinite(obs)).sum() + (~torch.isfinite(rew)).sum()
     omax = torch.maximum(omax, obs.abs().max())
     if i % 200 == 0:

@@ -7,6 +7,9 @@ run() { echo "== $*" >> $O; timeout -k 10 900 python3 scripts/soak.py "$@" >> $O
 run PickCube-v1 4096 5000 pd_joint_delta_pos
 run PickCube-v1 4096 3000 pd_ee_delta_pos
 run PickCube-v1 4096 3000 pd_ee_delta_pose
+run PickCube-v1 4096 2000 pd_ee_target_delta_pos
+run PickCube-v1 4096 2000 pd_ee_target_delta_pose
+run PickCube-v1 4096 2000 pd_ee_pose
 run PushCube-v1 4096 3000 pd_joint_delta_pos
 run PegInsertionSide-v1 2048 3000 pd_joint_delta_pos
 MS_ROBOT=fetch run Empty-v1 1024 2000 pd_joint_delta_pos
