@@ -72,6 +72,53 @@ typedef struct mssim_pusht_task {
 
 int mssim_task_pusht_outputs(mssim_handle h, const mssim_pusht_task* task, float* obs, float* reward, uint8_t* flags, float* intersection, void* stream);
 
+/* RollBall-style evaluate + state observation + dense reward in one launch (envs/tasks/tabletop/roll_ball.py).
+ * obs [N][2*n_dof+26] f32 (qpos, qvel, tcp_pose7, goal_pos3, ball_pose7, ball linear velocity 3, ball - tcp, goal - ball),
+ * reward [N] f32, flags [N][1] u8 = success (|ball - goal|_xy < goal_radius).
+ * The reward carries a per-env latch, `reached` (0 or 1), that lives in the caller's memory from step to step:
+ *   u = (ball - goal) / |ball - goal| (3-D), hit = ball + u (ball_radius + hit_offset), d = |hit - tcp|
+ *   update_reached != 0 and d < reach_thresh: reached = 1 (written in place)
+ *   r = 20 (1 - tanh |ball - goal|_xy) reached + (1 - tanh 2 d) (1 - reached) + reached; success: 30; times reward_scale
+ * With update_reached == 0 (the outputs of a reset) the latch is read and never written.
+ * This task and the next never run at the control-step kernel's tail: with a step_action + fetch owed, the control step
+ * and the copy-out + epilogue are two launches. */
+typedef struct mssim_roll_task {
+  int32_t tcp_row, ball_row, goal_row; /* rigid_body_data body rows */
+  float goal_radius;          /* 0.1   */
+  float ball_radius;          /* 0.035 */
+  float hit_offset;           /* 0.05: the hit point lies ball_radius + hit_offset behind the ball's centre, seen from the goal */
+  float reach_thresh;         /* 0.04  */
+  float reward_scale;         /* 1 (dense) or 1/30 (normalized_dense) */
+  float* reached;             /* device [N] f32, read and (update_reached != 0) written in place; required */
+  int32_t update_reached;
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;     /* optional device [N]: new elapsed_steps >= time_limit */
+  int32_t time_limit;
+  uint8_t* terminated_out;    /* optional device [N]: a copy of success */
+} mssim_roll_task;
+
+int mssim_task_roll_outputs(mssim_handle h, const mssim_roll_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
+
+/* PullCube-style evaluate + state observation + dense reward in one launch (envs/tasks/tabletop/pull_cube.py).
+ * obs [N][2*n_dof+17] f32 (qpos, qvel, tcp_pose7, goal_pos3, obj_pose7), reward [N] f32, flags [N][1] u8 = success
+ * (|obj - goal|_xy < goal_radius; no height condition).
+ *   d = |obj + (cube_half_size + 0.01, 0, 0) - tcp|; r = 1 - tanh 5 d; d < 0.01: + 1 - tanh 5 |obj - goal|_xy; success: 3;
+ *   times reward_scale */
+typedef struct mssim_pull_task {
+  int32_t tcp_row, obj_row, goal_row; /* rigid_body_data body rows */
+  float goal_radius;          /* 0.1  */
+  float cube_half_size;       /* 0.02 */
+  float reward_scale;         /* 1 (dense) or 1/3 (normalized_dense) */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;
+  int32_t time_limit;
+  uint8_t* terminated_out;
+} mssim_pull_task;
+
+int mssim_task_pull_outputs(mssim_handle h, const mssim_pull_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
+
 /* How many control steps of this handle so far ran as one launch with a task epilogue at the control-step kernel's
  * tail (a deferred step_action + fetch consumed by a task_*_outputs call), against the separate epilogue launch.
  * A host counter: no sync. */

@@ -6,8 +6,9 @@
 
 namespace mssim_dispatch {
 
-// TASK: 0 = plain control step; else the copy-out + that task's epilogue at the kernel's tail
-enum Task { kPlain = 0, kPick = 1, kPush = 2, kPeg = 3, kStack = 4, kPushT = 5, kNumTasks = 6 };
+// TASK: 0 = plain control step; else the copy-out + that task's epilogue at the kernel's tail. kRoll and kPull have no
+// row in kTails: their epilogue is always a launch of its own, tail_step() answers kNone for them.
+enum Task { kPlain = 0, kPick = 1, kPush = 2, kPeg = 3, kStack = 4, kPushT = 5, kRoll = 6, kPull = 7, kNumTasks = 8 };
 
 struct Key {
   int ndof;  // joints unrolled at compile time (9: the Panda, 7: panda_stick, 15: the Fetch), 0 = any topology

@@ -640,6 +640,101 @@ __global__ __launch_bounds__(256) void k_task_push(DevModel M, DevState S, mssim
   task_push_env(M, S, B, T, obs, reward, flags, e);
 }
 
+// RollBall evaluate / obs / reward (roll_ball.py evaluate, _get_obs_extra, compute_dense_reward, in its order of
+// operations). T.reached is the env's latch: read, set where the tcp is at the hit point (only with T.update_reached), and
+// read by the reward in its new value. One lane per env; never at the control-step kernel's tail.
+MS_DEV void task_roll_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_roll_task& T, float* __restrict__ obs, float* __restrict__ reward,
+                          uint8_t* __restrict__ flags, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 26);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  for (int j = 0; j < n; j++) {
+    o[j] = B.art_qpos[(size_t)e * n + j];
+    o[n + j] = B.art_qvel[(size_t)e * n + j];
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* bl = rowp(T.ball_row);
+  const float* gl = rowp(T.goal_row);
+  const f3 ptcp = f3{tcp[0], tcp[1], tcp[2]}, pball = f3{bl[0], bl[1], bl[2]}, pgoal = f3{gl[0], gl[1], gl[2]};
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  o[k++] = pgoal.x; o[k++] = pgoal.y; o[k++] = pgoal.z;
+  for (int i = 0; i < 7; i++) o[k++] = bl[i];
+  for (int i = 7; i < 10; i++) o[k++] = bl[i];
+  o[k++] = pball.x - ptcp.x; o[k++] = pball.y - ptcp.y; o[k++] = pball.z - ptcp.z;
+  o[k++] = pgoal.x - pball.x; o[k++] = pgoal.y - pball.y; o[k++] = pgoal.z - pball.z;
+  const float dx = pball.x - pgoal.x, dy = pball.y - pgoal.y;
+  const float ball_to_goal = sqrtf(dx * dx + dy * dy);
+  const bool success = ball_to_goal < T.goal_radius;
+  // the hit point: behind the ball, seen from the goal (the offset as the torch path forms it: the sum in double, rounded once)
+  const f3 away = pball - pgoal;
+  const float na = norm(away);
+  const f3 unit = f3{away.x / na, away.y / na, away.z / na};
+  const f3 hit = pball + unit * (float)((double)T.ball_radius + (double)T.hit_offset);
+  const float dist = norm(hit - ptcp);
+  float latch = T.reached[e];
+  if (T.update_reached && dist < T.reach_thresh) { latch = 1.f; T.reached[e] = 1.f; }
+  float r = 20.f * (1.f - tanhf(ball_to_goal)) * latch + (1.f - tanhf(2.f * dist)) * (1.f - latch) + latch;
+  if (success) r = 30.f;
+  reward[e] = r * T.reward_scale;
+  flags[e] = success;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_roll(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_roll_task T, float* __restrict__ obs, float* __restrict__ reward,
+                                                    uint8_t* __restrict__ flags) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_roll_env(M, S, B, T, obs, reward, flags, e);
+}
+
+// PullCube evaluate / obs / reward (pull_cube.py): PushCube's observation; the pull point lies behind the cube (+x), and
+// success has no height condition. One lane per env; never at the control-step kernel's tail.
+MS_DEV void task_pull_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_pull_task& T, float* __restrict__ obs, float* __restrict__ reward,
+                          uint8_t* __restrict__ flags, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 17);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  for (int j = 0; j < n; j++) {
+    o[j] = B.art_qpos[(size_t)e * n + j];
+    o[n + j] = B.art_qvel[(size_t)e * n + j];
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* ob = rowp(T.obj_row);
+  const float* gl = rowp(T.goal_row);
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  for (int i = 0; i < 3; i++) o[k++] = gl[i];
+  for (int i = 0; i < 7; i++) o[k++] = ob[i];
+  const float dx = ob[0] - gl[0], dy = ob[1] - gl[1];
+  const float obj_to_goal = sqrtf(dx * dx + dy * dy);
+  const bool success = obj_to_goal < T.goal_radius;
+  // (the offset as the torch path forms it: half + 2 x 5 mm in double, rounded once)
+  const f3 pull_p = f3{ob[0] + (float)((double)T.cube_half_size + 0.01), ob[1], ob[2]};
+  const float dist = norm(pull_p - f3{tcp[0], tcp[1], tcp[2]});
+  float r = 1.f - tanhf(5.f * dist);
+  if (dist < 0.01f) r += 1.f - tanhf(5.f * obj_to_goal);
+  if (success) r = 3.f;
+  reward[e] = r * T.reward_scale;
+  flags[e] = success;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_pull(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_pull_task T, float* __restrict__ obs, float* __restrict__ reward,
+                                                    uint8_t* __restrict__ flags) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_pull_env(M, S, B, T, obs, reward, flags, e);
+}
+
 // Pose algebra exactly as the Python `Pose` class does it (utils/structs/pose.py, rotation_conversions.py:
 // no re-normalisation, rotation as p + w t + v x t with t = 2 v x p, product standardised to w >= 0), so
 // that the fused task outputs equal the torch path also for the slightly non-unit quaternions users set
@@ -1519,7 +1614,7 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
   return 0;
 }
 
-// A task epilogue, the one sequence behind the five mssim_task_*_outputs. Refusals come first and leave what is owed owed.
+// A task epilogue, the one sequence behind the seven mssim_task_*_outputs. Refusals come first and leave what is owed owed.
 // An owed step_action + an owed fetch + the epilogue = ONE launch of the control-step kernel, where mssim_create found an
 // instance with the task's tail for the model (h->tail_fn). Otherwise what is owed is performed and the epilogue is a launch
 // of its own: `standalone(std::true_type, what, st)` launches k_task_*<true>, which first performs the owed copy-out `what`,
@@ -1533,9 +1628,9 @@ struct TaskCall {
 };
 extern "C++" {
 using TailTask = decltype(DevState::tail_task);
-// rows: the body rows the task reads; slot: the task's member of the tail_task union
-template <class Task, size_t NROWS, class Standalone>
-static int task_outputs(mssim_handle h, const TaskCall& c, Task TailTask::*slot, const Task* task, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
+// the refusals of a task call; rows: the body rows the task reads
+template <size_t NROWS>
+static int task_refusals(mssim_handle h, const TaskCall& c, const int (&rows)[NROWS]) {
   const int R = h->M.n_link + h->M.n_free + h->M.n_kin;
   for (int r : rows)
     if (r < 0 || r >= R) { h->err = std::string("task_") + c.name + "_outputs: body row out of range"; return 1; }
@@ -1543,6 +1638,23 @@ static int task_outputs(mssim_handle h, const TaskCall& c, Task TailTask::*slot,
   if (c.refused) { h->err = c.refused; return 3; }
   if (c.pair_rows)
     if (int rc = finger_pair_list(h, c.pair_rows[0], c.pair_rows[1], c.pair_rows[2])) return rc;
+  return 0;
+}
+// The tail-less path, for a task without a member in the tail_task union (RollBall, PullCube: h->tail_fn[c.id] is null
+// for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
+template <size_t NROWS, class Standalone>
+static int task_outputs(mssim_handle h, const TaskCall& c, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
+  if (int rc = task_refusals(h, c, rows)) return rc;
+  settle(h, st, /*keep_fetch=*/true);
+  if (const unsigned what = std::exchange(h->owed.fetch, 0u)) standalone(std::true_type{}, what, st);
+  else standalone(std::false_type{}, 0u, st);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// slot: the task's member of the tail_task union
+template <class Task, size_t NROWS, class Standalone>
+static int task_outputs(mssim_handle h, const TaskCall& c, Task TailTask::*slot, const Task* task, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
+  if (int rc = task_refusals(h, c, rows)) return rc;
   const Owed& o = h->owed;
   if (h->tail_fn[c.id] && o.action && o.fetch && o.nsub > 0 && st == o.stream && h->ee.link < 0 && h->ik.link < 0) {
     DevState S = state_with_action(h, o.action, o.adim);
@@ -1618,6 +1730,26 @@ int mssim_task_pusht_outputs(mssim_handle h, const mssim_pusht_task* task, float
     // 16 lanes per env: 16 envs per block of 256
     hipLaunchKernelGGL(k_task_pusht<decltype(fetch)::value>, env_grid(h->N, 16), dim3(256), 0, st,
                        h->M, h->S, h->buf, what, *task, obs, reward, flags, intersection);
+  });
+}
+
+int mssim_task_roll_outputs(mssim_handle h, const mssim_roll_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
+  const int rows[] = {task->tcp_row, task->ball_row, task->goal_row};
+  const TaskCall call{mssim_dispatch::kRoll, "roll", task->reached ? nullptr : "task_roll_outputs: needs the reached latch (device [N] f32)", /*pair_rows=*/nullptr,
+                      obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    // an env per lane as k_task_push: 256 envs per block, 64 behind the copy-out
+    hipLaunchKernelGGL(k_task_roll<decltype(fetch)::value>, env_grid(h->N, fetch ? 64 : 256), dim3(256), 0, st,
+                       h->M, h->S, h->buf, what, *task, obs, reward, flags);
+  });
+}
+
+int mssim_task_pull_outputs(mssim_handle h, const mssim_pull_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
+  const int rows[] = {task->tcp_row, task->obj_row, task->goal_row};
+  const TaskCall call{mssim_dispatch::kPull, "pull", /*refused=*/nullptr, /*pair_rows=*/nullptr, obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    hipLaunchKernelGGL(k_task_pull<decltype(fetch)::value>, env_grid(h->N, fetch ? 64 : 256), dim3(256), 0, st,
+                       h->M, h->S, h->buf, what, *task, obs, reward, flags);
   });
 }
 

@@ -167,6 +167,21 @@ class PushTTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class RollTask(C.Structure):
+    """mssim_roll_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("ball_row", C.c_int32), ("goal_row", C.c_int32),
+                ("goal_radius", C.c_float), ("ball_radius", C.c_float), ("hit_offset", C.c_float), ("reach_thresh", C.c_float),
+                ("reward_scale", C.c_float), ("reached", C.c_void_p), ("update_reached", C.c_int32),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
+class PullTask(C.Structure):
+    """mssim_pull_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("obj_row", C.c_int32), ("goal_row", C.c_int32), ("goal_radius", C.c_float),
+                ("cube_half_size", C.c_float), ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
 class EeIkMap(C.Structure):
     """mssim_ee_ik_map of include/mssim_hip_tasks.h (HIP library only)"""
     _fields_ = [("link_index", C.c_int32), ("column0", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32),
@@ -234,6 +249,8 @@ class NativeLib:
         for name, restype, argtypes in (
             ("task_stack_outputs", C.c_int, [H, C.POINTER(StackTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_pusht_outputs", C.c_int, [H, C.POINTER(PushTTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_roll_outputs", C.c_int, [H, C.POINTER(RollTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_pull_outputs", C.c_int, [H, C.POINTER(PullTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
             ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
             ("ee_ik_solve", C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -396,6 +413,16 @@ class NativeSim:
         if self.lib.task_pusht_outputs is None:
             raise NativeError(f"{self.lib.path} has no task_pusht_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.task_pusht_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, intersection_ptr, stream), "task_pusht_outputs")
+
+    def task_roll_outputs(self, task: "RollTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
+        if self.lib.task_roll_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_roll_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_roll_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_roll_outputs")
+
+    def task_pull_outputs(self, task: "PullTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
+        if self.lib.task_pull_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_pull_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_pull_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_pull_outputs")
 
     def tail_step_count(self) -> int:
         """control steps that ran with the task epilogue at the control-step kernel's tail (HIP library only)"""

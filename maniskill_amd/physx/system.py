@@ -383,6 +383,15 @@ class MssimSystem:
         self._sim.task_pusht_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(),
                                      None if intersection is None else intersection.data_ptr(), self._stream())
 
+    def task_roll_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
+        """RollBall evaluate / obs / reward in one launch; the struct points to the env's `reached_status` latch
+        (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_roll_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
+
+    def task_pull_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
+        """PullCube evaluate / obs / reward in one launch (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_pull_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
+
     def tail_step_count(self) -> int:
         """control steps so far that ran as one launch with the task epilogue at the kernel's tail (HIP library only)"""
         return self._sim.tail_step_count()
