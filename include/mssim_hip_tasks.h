@@ -119,6 +119,65 @@ typedef struct mssim_pull_task {
 
 int mssim_task_pull_outputs(mssim_handle h, const mssim_pull_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
 
+/* PokeCube-style evaluate + state observation + dense reward in one launch (envs/tasks/tabletop/poke_cube.py,
+ * agents/robots/panda/panda.py is_grasping / is_static). Reads the user-visible buffers (after fetch) and the last substep's
+ * finger <-> peg contact impulses. The model has two free bodies (two rows of the control-step kernel per env); like the two
+ * tasks above, this one and the next never run at the control-step kernel's tail.
+ * obs [N][2*n_dof+36] f32 (qpos, qvel, tcp_pose7, cube_pose7, peg_pose7, "goal_pos" = the PEG's position 3, peg - tcp,
+ * cube - peg, goal - cube, peg head - cube, the head being peg + (peg_half_length, 0, 0), unrotated),
+ * reward [N] f32, flags [N][4] u8 = success, is_cube_placed, is_peg_cube_fit, is_peg_grasped,
+ * metrics [N][2] f32 = angle_diff, head_to_cube_dist; required.
+ *   yaw(q) = atan2(-R01, R00) of the rotation matrix of q (entries scaled by 2 / |q|^2): the third XYZ Euler angle
+ *   angle_diff = |yaw(peg * head offset) - yaw(cube)| (not wrapped); head_to_cube_dist = |head - cube|_xy
+ *   placed = |cube - goal|_xy < goal_radius; fit = angle_diff < align_thresh and head_to_cube_dist <= cube_half_size +
+ *   0.005; static = max |qvel[:n_static_dofs]| <= static_thresh; success = placed and static
+ *   r = 2 (1 - tanh 5 |tcp - peg|); grasped and |tcp - peg| < reach_thresh: r = 4 + (1 - tanh 5 head_to_cube_dist) +
+ *   (1 - tanh 5 angle_diff); and fit: r = 7 + (1 - tanh 5 |goal - cube|); placed: r += 1 - tanh 5 |qvel[:n_static_dofs]|;
+ *   success: 10; times reward_scale */
+typedef struct mssim_poke_task {
+  int32_t tcp_row, peg_row, cube_row, goal_row, finger1_row, finger2_row; /* rigid_body_data body rows */
+  int32_t n_static_dofs;      /* leading joints of is_static and of the static reward (all but the two fingers) */
+  float peg_half_length;      /* 0.12: the head offset along the peg's x axis                                   */
+  float cube_half_size;       /* 0.02: the head is close within this + 0.005 (the sum formed in double, rounded once) */
+  float goal_radius;          /* 0.05 */
+  float align_thresh;         /* 0.05 rad */
+  float reach_thresh;         /* 0.01 */
+  float static_thresh;        /* 0.2 rad/s */
+  float min_force;            /* 0.5 N  (is_grasping of the peg) */
+  float max_angle_deg;        /* 85 */
+  float reward_scale;         /* 1 (dense) or 1/10 (normalized_dense) */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;     /* optional device [N]: new elapsed_steps >= time_limit */
+  int32_t time_limit;
+  uint8_t* terminated_out;    /* optional device [N]: a copy of success */
+} mssim_poke_task;
+
+int mssim_task_poke_outputs(mssim_handle h, const mssim_poke_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream);
+
+/* LiftPegUpright-style evaluate + state observation + dense reward in one launch
+ * (envs/tasks/tabletop/lift_peg_upright.py, Panda.is_grasping).
+ * obs [N][2*n_dof+14] f32 (qpos, qvel, tcp_pose7, obj_pose7), reward [N] f32, flags [N][1] u8 = success:
+ *   | |yaw(peg)| - pi/2 | < upright_thresh (yaw as above) and |peg_z - peg_half_length| < height_thresh
+ *   r = |R20| + (1 - tanh 5 |peg_z - peg_half_length|) + (grasped ? 1 : 1 - tanh 5 |peg - tcp|) / 5; success: 3;
+ *   times reward_scale */
+typedef struct mssim_liftpeg_task {
+  int32_t tcp_row, peg_row, finger1_row, finger2_row; /* rigid_body_data body rows */
+  float peg_half_length;      /* 0.12  */
+  float upright_thresh;       /* 0.08 rad */
+  float height_thresh;        /* 0.005 */
+  float min_force;            /* 0.5 N  (is_grasping of the peg) */
+  float max_angle_deg;        /* 85 */
+  float reward_scale;         /* 1 (dense) or 1/3 (normalized_dense) */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;
+  int32_t time_limit;
+  uint8_t* terminated_out;
+} mssim_liftpeg_task;
+
+int mssim_task_liftpeg_outputs(mssim_handle h, const mssim_liftpeg_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
+
 /* How many control steps of this handle so far ran as one launch with a task epilogue at the control-step kernel's
  * tail (a deferred step_action + fetch consumed by a task_*_outputs call), against the separate epilogue launch.
  * A host counter: no sync. */

@@ -6,9 +6,10 @@
 
 namespace mssim_dispatch {
 
-// TASK: 0 = plain control step; else the copy-out + that task's epilogue at the kernel's tail. kRoll and kPull have no
-// row in kTails: their epilogue is always a launch of its own, tail_step() answers kNone for them.
-enum Task { kPlain = 0, kPick = 1, kPush = 2, kPeg = 3, kStack = 4, kPushT = 5, kRoll = 6, kPull = 7, kNumTasks = 8 };
+// TASK: 0 = plain control step; else the copy-out + that task's epilogue at the kernel's tail. kRoll, kPull, kPoke
+// and kLiftPeg have no row in kTails: their epilogue is always a launch of its own, tail_step() answers kNone for them
+// (kPoke on the two-row plain step, the other three on the one-row one).
+enum Task { kPlain = 0, kPick = 1, kPush = 2, kPeg = 3, kStack = 4, kPushT = 5, kRoll = 6, kPull = 7, kPoke = 8, kLiftPeg = 9, kNumTasks = 10 };
 
 struct Key {
   int ndof;  // joints unrolled at compile time (9: the Panda, 7: panda_stick, 15: the Fetch), 0 = any topology

@@ -902,6 +902,155 @@ __global__ __launch_bounds__(256) void k_task_stack(DevModel M, DevState S, mssi
   task_stack_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
 }
 
+// Panda.is_grasping from the finger <-> object contact forces of the last substep, as task_pick_env computes it (the pair
+// list is finger_pair_list's); f1 / f2: the fingers' rigid_body_data rows of env e.
+// task_pick_env, task_peg_env and task_stack_env still carry this block inline: they are compiled into k_solve16 instances,
+// which stay byte for byte as they are here. They should move to this helper in a change of their own; until then a fix to
+// the block has to be made in all four places.
+MS_DEV bool fingers_grasp(const DevModel& M, const DevState& S, const int* __restrict__ pairs, int npairs, const float* f1, const float* f2, float min_force,
+                          float max_angle_deg, int e) {
+  const int N = S.N;
+  f3 lf = f3{0, 0, 0}, rf = f3{0, 0, 0};
+  for (int k = 0; k < npairs; k++) {
+    const unsigned ent = (unsigned)pairs[k];
+    const int p = (int)(ent & 0x3FFFFFFFu);
+    if (S.pair_cnt[(size_t)p * N + e] <= 0) continue;
+    f3 imp = f3{SOA(S.pair_imp, 3 * p), SOA(S.pair_imp, 3 * p + 1), SOA(S.pair_imp, 3 * p + 2)} * ((ent >> 31) ? -1.f : 1.f);
+    if ((ent >> 30) & 1u) rf += imp; else lf += imp;
+  }
+  const float inv_dt = 1.f / M.dt;
+  lf = lf * inv_dt; rf = rf * inv_dt;
+  auto yaxis = [&](const float* r) { return mcol(qmat(qnormalized(q4{r[3], r[4], r[5], r[6]})), 1); };
+  auto angle_deg = [&](f3 a, f3 b) {
+    const float na = norm(a), nb = norm(b);
+    a = a * (1.f / (na < 1e-6f ? 1.f : na));
+    b = b * (1.f / (nb < 1e-6f ? 1.f : nb));
+    return acosf(fminf(fmaxf(dot(a, b), -1.f), 1.f)) * 57.29577951308232f;
+  };
+  const f3 ldir = yaxis(f1), rdir = -yaxis(f2);
+  return norm(lf) >= min_force && angle_deg(ldir, lf) <= max_angle_deg && norm(rf) >= min_force && angle_deg(rdir, rf) <= max_angle_deg;
+}
+// The third angle of the XYZ Tait-Bryan decomposition of q's rotation matrix, atan2(-R01, R00), with the two entries as
+// rotation_conversions.quaternion_to_matrix forms them: scaled by 2 / |q|^2, no unit norm assumed
+MS_DEV float tq_euler_z(q4 q) {
+  const float two_s = 2.f / (q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+  const float r00 = 1.f - two_s * (q.y * q.y + q.z * q.z);
+  const float r01 = two_s * (q.x * q.y - q.z * q.w);
+  return atan2f(-r01, r00);
+}
+
+// PokeCube evaluate / obs / reward (poke_cube.py evaluate, _get_obs_extra, compute_dense_reward, in its order of masks).
+// The head position is peg + (half length, 0, 0) unrotated; only the quaternion of the head POSE (peg * offset) is read.
+// One lane per env; never at the control-step kernel's tail.
+MS_DEV void task_poke_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_poke_task& T, const int* __restrict__ pairs, int npairs,
+                          float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 36);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  float qv_max = 0.f, qv_sq = 0.f;
+  for (int j = 0; j < n; j++) {
+    const float q = B.art_qpos[(size_t)e * n + j], v = B.art_qvel[(size_t)e * n + j];
+    o[j] = q;
+    o[n + j] = v;
+    if (j < T.n_static_dofs) { qv_max = fmaxf(qv_max, fabsf(v)); qv_sq += v * v; }
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* pg = rowp(T.peg_row);
+  const float* cb = rowp(T.cube_row);
+  const float* gl = rowp(T.goal_row);
+  const f3 ptcp = f3{tcp[0], tcp[1], tcp[2]}, ppeg = f3{pg[0], pg[1], pg[2]}, pcube = f3{cb[0], cb[1], cb[2]}, pgoal = f3{gl[0], gl[1], gl[2]};
+  const f3 phead = f3{ppeg.x + T.peg_half_length, ppeg.y, ppeg.z};
+  const bool grasped = fingers_grasp(M, S, pairs, npairs, rowp(T.finger1_row), rowp(T.finger2_row), T.min_force, T.max_angle_deg, e);
+  // evaluate
+  const float gx = pcube.x - pgoal.x, gy = pcube.y - pgoal.y;
+  const bool placed = sqrtf(gx * gx + gy * gy) < T.goal_radius;
+  const pose_t head = tq_mul(pose_t{ppeg, q4{pg[3], pg[4], pg[5], pg[6]}}, pose_t{f3{T.peg_half_length, 0, 0}, q4{1, 0, 0, 0}});
+  const float angle_diff = fabsf(tq_euler_z(head.q) - tq_euler_z(q4{cb[3], cb[4], cb[5], cb[6]}));
+  const float hx = phead.x - pcube.x, hy = phead.y - pcube.y;
+  const float head_to_cube = sqrtf(hx * hx + hy * hy);
+  // (the threshold as the torch path forms it: half + 5 mm in double, rounded once)
+  const bool fit = angle_diff < T.align_thresh && head_to_cube <= (float)((double)T.cube_half_size + 5e-3);
+  const bool is_static = qv_max <= T.static_thresh;
+  const bool success = placed && is_static;
+  // observation
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  for (int i = 0; i < 7; i++) o[k++] = cb[i];
+  for (int i = 0; i < 7; i++) o[k++] = pg[i];
+  o[k++] = ppeg.x; o[k++] = ppeg.y; o[k++] = ppeg.z;  // "goal_pos": the peg's position
+  o[k++] = ppeg.x - ptcp.x; o[k++] = ppeg.y - ptcp.y; o[k++] = ppeg.z - ptcp.z;
+  o[k++] = pcube.x - ppeg.x; o[k++] = pcube.y - ppeg.y; o[k++] = pcube.z - ppeg.z;
+  o[k++] = pgoal.x - pcube.x; o[k++] = pgoal.y - pcube.y; o[k++] = pgoal.z - pcube.z;
+  o[k++] = phead.x - pcube.x; o[k++] = phead.y - pcube.y; o[k++] = phead.z - pcube.z;
+  // dense reward: each tier replaces the one before
+  const float tcp_to_peg = norm(ptcp - ppeg);
+  float r = 2.f * (1.f - tanhf(5.f * tcp_to_peg));
+  const bool held = grasped && tcp_to_peg < T.reach_thresh;
+  if (held) r = 4.f + (1.f - tanhf(5.f * head_to_cube)) + (1.f - tanhf(5.f * angle_diff));
+  if (fit && held) r = 7.f + (1.f - tanhf(5.f * norm(pgoal - pcube)));
+  if (placed) r += 1.f - tanhf(5.f * sqrtf(qv_sq));
+  if (success) r = 10.f;
+  reward[e] = r * T.reward_scale;
+  uint8_t* f = flags + 4 * (size_t)e;
+  f[0] = success; f[1] = placed; f[2] = fit; f[3] = grasped;
+  metrics[2 * (size_t)e] = angle_diff; metrics[2 * (size_t)e + 1] = head_to_cube;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_poke(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_poke_task T, const int* __restrict__ pairs, int npairs,
+                                                    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_poke_env(M, S, B, T, pairs, npairs, obs, reward, flags, metrics, e);
+}
+
+// LiftPegUpright evaluate / obs / reward (lift_peg_upright.py): upright = the third XYZ Euler angle within upright_thresh of
+// +-pi/2 (pi/2 as float32, what the torch path subtracts); the rotation term |R20| is the z component of the peg's x axis.
+// One lane per env; never at the control-step kernel's tail.
+MS_DEV void task_liftpeg_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_liftpeg_task& T, const int* __restrict__ pairs, int npairs,
+                             float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 14);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  for (int j = 0; j < n; j++) {
+    o[j] = B.art_qpos[(size_t)e * n + j];
+    o[n + j] = B.art_qvel[(size_t)e * n + j];
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* pg = rowp(T.peg_row);
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  for (int i = 0; i < 7; i++) o[k++] = pg[i];
+  const bool grasped = fingers_grasp(M, S, pairs, npairs, rowp(T.finger1_row), rowp(T.finger2_row), T.min_force, T.max_angle_deg, e);
+  const q4 q = q4{pg[3], pg[4], pg[5], pg[6]};
+  const float z_dist = fabsf(pg[2] - T.peg_half_length);
+  const bool success = fabsf(fabsf(tq_euler_z(q)) - 1.5707963267948966f) < T.upright_thresh && z_dist < T.height_thresh;
+  const float two_s = 2.f / (q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+  float r = fabsf(two_s * (q.x * q.z - q.y * q.w));
+  r += 1.f - tanhf(5.f * z_dist);
+  const float reaching = grasped ? 1.f : 1.f - tanhf(5.f * norm(f3{pg[0], pg[1], pg[2]} - f3{tcp[0], tcp[1], tcp[2]}));
+  r += reaching / 5.f;
+  if (success) r = 3.f;
+  reward[e] = r * T.reward_scale;
+  flags[e] = success;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_liftpeg(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_liftpeg_task T, const int* __restrict__ pairs, int npairs,
+                                                       float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_liftpeg_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
+}
+
 // PushT pseudo-render (push_t.py pseudo_render_intersection): every template pixel (i, j) of the block's T, at its uv
 // grid centre (U[j], V[i], 1), is mapped by world_to_goal @ tee_to_world, divided by the third row, scaled to pixel
 // indices and truncated toward zero (.long()); an index outside [0, 64) sends the pixel to (0, 0). Index pair (x, y)
@@ -1614,7 +1763,7 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
   return 0;
 }
 
-// A task epilogue, the one sequence behind the seven mssim_task_*_outputs. Refusals come first and leave what is owed owed.
+// A task epilogue, the one sequence behind the nine mssim_task_*_outputs. Refusals come first and leave what is owed owed.
 // An owed step_action + an owed fetch + the epilogue = ONE launch of the control-step kernel, where mssim_create found an
 // instance with the task's tail for the model (h->tail_fn). Otherwise what is owed is performed and the epilogue is a launch
 // of its own: `standalone(std::true_type, what, st)` launches k_task_*<true>, which first performs the owed copy-out `what`,
@@ -1640,8 +1789,8 @@ static int task_refusals(mssim_handle h, const TaskCall& c, const int (&rows)[NR
     if (int rc = finger_pair_list(h, c.pair_rows[0], c.pair_rows[1], c.pair_rows[2])) return rc;
   return 0;
 }
-// The tail-less path, for a task without a member in the tail_task union (RollBall, PullCube: h->tail_fn[c.id] is null
-// for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
+// The tail-less path, for a task without a member in the tail_task union (RollBall, PullCube, PokeCube, LiftPegUpright:
+// h->tail_fn[c.id] is null for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
 template <size_t NROWS, class Standalone>
 static int task_outputs(mssim_handle h, const TaskCall& c, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
   if (int rc = task_refusals(h, c, rows)) return rc;
@@ -1750,6 +1899,28 @@ int mssim_task_pull_outputs(mssim_handle h, const mssim_pull_task* task, float* 
   return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
     hipLaunchKernelGGL(k_task_pull<decltype(fetch)::value>, env_grid(h->N, fetch ? 64 : 256), dim3(256), 0, st,
                        h->M, h->S, h->buf, what, *task, obs, reward, flags);
+  });
+}
+
+int mssim_task_poke_outputs(mssim_handle h, const mssim_poke_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream) {
+  const int rows[] = {task->tcp_row, task->peg_row, task->cube_row, task->goal_row, task->finger1_row, task->finger2_row};
+  const int pair_rows[] = {task->peg_row, task->finger1_row, task->finger2_row};
+  const TaskCall call{mssim_dispatch::kPoke, "poke", metrics ? nullptr : "task_poke_outputs: needs the metrics output (device [N][2] f32)", pair_rows,
+                      obs, reward, flags, metrics};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    // launch shapes as mssim_task_pick_outputs
+    hipLaunchKernelGGL(k_task_poke<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, metrics);
+  });
+}
+
+int mssim_task_liftpeg_outputs(mssim_handle h, const mssim_liftpeg_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
+  const int rows[] = {task->tcp_row, task->peg_row, task->finger1_row, task->finger2_row};
+  const int pair_rows[] = {task->peg_row, task->finger1_row, task->finger2_row};
+  const TaskCall call{mssim_dispatch::kLiftPeg, "liftpeg", /*refused=*/nullptr, pair_rows, obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    hipLaunchKernelGGL(k_task_liftpeg<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags);
   });
 }
 

@@ -1,2 +1,2 @@
-from .tabletop import PegInsertionSideEnv, PickCubeEnv, PullCubeEnv, PushCubeEnv, PushTEnv, RollBallEnv, StackCubeEnv
+from .tabletop import LiftPegUprightEnv, PegInsertionSideEnv, PickCubeEnv, PokeCubeEnv, PullCubeEnv, PushCubeEnv, PushTEnv, RollBallEnv, StackCubeEnv
 from .empty_env import EmptyEnv

@@ -182,6 +182,22 @@ class PullTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class PokeTask(C.Structure):
+    """mssim_poke_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("peg_row", C.c_int32), ("cube_row", C.c_int32), ("goal_row", C.c_int32), ("finger1_row", C.c_int32), ("finger2_row", C.c_int32),
+                ("n_static_dofs", C.c_int32), ("peg_half_length", C.c_float), ("cube_half_size", C.c_float), ("goal_radius", C.c_float), ("align_thresh", C.c_float),
+                ("reach_thresh", C.c_float), ("static_thresh", C.c_float), ("min_force", C.c_float), ("max_angle_deg", C.c_float), ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
+class LiftPegTask(C.Structure):
+    """mssim_liftpeg_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("peg_row", C.c_int32), ("finger1_row", C.c_int32), ("finger2_row", C.c_int32),
+                ("peg_half_length", C.c_float), ("upright_thresh", C.c_float), ("height_thresh", C.c_float), ("min_force", C.c_float), ("max_angle_deg", C.c_float),
+                ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
 class EeIkMap(C.Structure):
     """mssim_ee_ik_map of include/mssim_hip_tasks.h (HIP library only)"""
     _fields_ = [("link_index", C.c_int32), ("column0", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32),
@@ -251,6 +267,8 @@ class NativeLib:
             ("task_pusht_outputs", C.c_int, [H, C.POINTER(PushTTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_roll_outputs", C.c_int, [H, C.POINTER(RollTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_pull_outputs", C.c_int, [H, C.POINTER(PullTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_poke_outputs", C.c_int, [H, C.POINTER(PokeTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_liftpeg_outputs", C.c_int, [H, C.POINTER(LiftPegTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
             ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
             ("ee_ik_solve", C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -423,6 +441,16 @@ class NativeSim:
         if self.lib.task_pull_outputs is None:
             raise NativeError(f"{self.lib.path} has no task_pull_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.task_pull_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_pull_outputs")
+
+    def task_poke_outputs(self, task: "PokeTask", obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream=None):
+        if self.lib.task_poke_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_poke_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_poke_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream), "task_poke_outputs")
+
+    def task_liftpeg_outputs(self, task: "LiftPegTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
+        if self.lib.task_liftpeg_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_liftpeg_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_liftpeg_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_liftpeg_outputs")
 
     def tail_step_count(self) -> int:
         """control steps that ran with the task epilogue at the control-step kernel's tail (HIP library only)"""

@@ -392,6 +392,15 @@ class MssimSystem:
         """PullCube evaluate / obs / reward in one launch (include/mssim_hip_tasks.h; HIP library only)"""
         self._sim.task_pull_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
 
+    def task_poke_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor, metrics: Optional[torch.Tensor]):
+        """PokeCube evaluate / obs / reward in one launch; metrics [N][2] f32 = angle_diff, head_to_cube_dist, required
+        (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_poke_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), None if metrics is None else metrics.data_ptr(), self._stream())
+
+    def task_liftpeg_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
+        """LiftPegUpright evaluate / obs / reward in one launch (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_liftpeg_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
+
     def tail_step_count(self) -> int:
         """control steps so far that ran as one launch with the task epilogue at the kernel's tail (HIP library only)"""
         return self._sim.tail_step_count()

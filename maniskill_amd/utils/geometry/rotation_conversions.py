@@ -146,3 +146,28 @@ def matrix_to_axis_angle(matrix: torch.Tensor) -> torch.Tensor:
 
 def euler_angles_to_quaternion(euler_angles: torch.Tensor, convention: str = "XYZ") -> torch.Tensor:
     return matrix_to_quaternion(euler_angles_to_matrix(euler_angles, convention))
+
+
+def matrix_to_euler_angles(matrix: torch.Tensor, convention: str) -> torch.Tensor:
+    """the inverse of `euler_angles_to_matrix` for the six Tait-Bryan conventions (three different axes): with
+    R = R_i(a) R_j(b) R_k(c) and s = +1 for a cyclic order of (i, j, k), -1 otherwise,
+      R[i, k] = s sin b,  R[j, k] = -s cos b sin a,  R[k, k] = cos b cos a,  R[i, j] = -s cos b sin c,  R[i, i] = cos b cos c
+    so (a, b, c) = (atan2(-s R[j, k], R[k, k]), asin(s R[i, k]), atan2(-s R[i, j], R[i, i])); "XYZ":
+    (atan2(-R12, R22), asin(R02), atan2(-R01, R00)). The middle angle comes back in [-pi/2, pi/2]. Proper Euler
+    conventions (first axis = last axis) are not implemented."""
+    if len(convention) != 3:
+        raise ValueError("Convention must have 3 letters.")
+    if any(c not in "XYZ" for c in convention):
+        raise ValueError(f"Invalid letter in convention string {convention}.")
+    if convention[1] in (convention[0], convention[2]):
+        raise ValueError(f"Invalid convention {convention}.")
+    if matrix.size(-1) != 3 or matrix.size(-2) != 3:
+        raise ValueError(f"Invalid rotation matrix shape {matrix.shape}.")
+    i, j, k = ("XYZ".index(c) for c in convention)
+    if i == k:
+        raise NotImplementedError(f"proper Euler convention {convention}: only the Tait-Bryan conventions are implemented")
+    s = 1.0 if (j - i) % 3 == 1 else -1.0
+    first = torch.atan2(-s * matrix[..., j, k], matrix[..., k, k])
+    middle = torch.asin(s * matrix[..., i, k])
+    last = torch.atan2(-s * matrix[..., i, j], matrix[..., i, i])
+    return torch.stack((first, middle, last), -1)
