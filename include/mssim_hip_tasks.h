@@ -178,6 +178,72 @@ typedef struct mssim_liftpeg_task {
 
 int mssim_task_liftpeg_outputs(mssim_handle h, const mssim_liftpeg_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
 
+/* PlaceSphere-style evaluate + state observation + dense reward in one launch (envs/tasks/tabletop/place_sphere.py,
+ * Panda.is_grasping / is_static, Actor.is_static). Reads the user-visible buffers (after fetch) and the last substep's
+ * finger <-> sphere contact impulses. Like the four tasks above, this one and the next never run at the control-step
+ * kernel's tail.
+ * obs [N][2*n_dof+21] f32 (qpos, qvel, is_grasped as 0 / 1, tcp_pose7, bin_pos3, obj_pose7, obj - tcp),
+ * reward [N] f32, flags [N][4] u8 = success, is_obj_grasped, is_obj_on_bin, is_obj_static.
+ *   off = obj - bin; on_bin = |off|_xy <= on_bin_tol and |off_z - radius - bin_base_half| <= on_bin_tol
+ *   static = |v_obj| <= static_lin_thresh and |w_obj| <= static_ang_thresh; success = on_bin and static and not grasped
+ *   r = 2 (1 - tanh 5 |tcp - obj|); grasped: r = 4 + (1 - tanh 5 |bin + (bin_base_half + radius) z - obj|);
+ *   on_bin: r = 6 + (ungrasp + (1 - tanh(10 |v_obj| + |w_obj|)) + robot_static) / 3 with ungrasp = (sum of the two finger
+ *   joints) / gripper_width if grasped, else 16, and robot_static = 1 where max |qvel[:n_static_dofs]| <=
+ *   robot_static_thresh, else 0; success: 13; times reward_scale.
+ * Refused (rc 3) for a model with fewer than two joints or gripper_width <= 0, as mssim_task_stack_outputs. */
+typedef struct mssim_place_task {
+  int32_t tcp_row, obj_row, bin_row, finger1_row, finger2_row; /* rigid_body_data body rows */
+  int32_t n_static_dofs;      /* leading joints of the robot's is_static (all but the two fingers) */
+  float radius;               /* 0.02: the sphere's                                                  */
+  float bin_base_half;        /* 0.0025: half the thickness of the bin's bottom block                */
+  float on_bin_tol;           /* 0.005: both the xy and the z tolerance of is_obj_on_bin             */
+  float static_lin_thresh;    /* 1e-2 m/s  */
+  float static_ang_thresh;    /* 0.5 rad/s */
+  float robot_static_thresh;  /* 0.2 rad/s */
+  float gripper_width;        /* fully open finger gap (2 x the last joint's upper limit) */
+  float min_force;            /* 0.5 N  (is_grasping of the sphere) */
+  float max_angle_deg;        /* 85 */
+  float reward_scale;         /* 1 (dense) or 1/13 (normalized_dense) */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;     /* optional device [N]: new elapsed_steps >= time_limit */
+  int32_t time_limit;
+  uint8_t* terminated_out;    /* optional device [N]: a copy of success */
+} mssim_place_task;
+
+int mssim_task_place_outputs(mssim_handle h, const mssim_place_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
+
+/* PullCubeTool-style evaluate + state observation + dense reward in one launch (envs/tasks/tabletop/pull_cube_tool.py,
+ * Panda.is_grasping). The tool is one body row with two shapes; the model has two free bodies (two rows of the
+ * control-step kernel per env).
+ * obs [N][2*n_dof+21] f32 (qpos, qvel, tcp_pose7, cube_pose7, tool_pose7), reward [N] f32, flags [N][1] u8 = success,
+ * metrics [N][3] f32 = cube_to_workspace_dist, 1 - tanh(3 cube_to_workspace_dist), dense reward / 5; required.
+ *   success = |cube - base|_xy < pulled_close_dist; cube_to_workspace_dist = |cube - (base + (0.1 arm_reach, 0, 0))|
+ *   d_t = |tcp - (tool + (0.02, 0, 0))|, g = 1 where the tool is grasped, else 0
+ *   d_p = |tool - (cube + (-(hook_length + cube_half_size), -0.067, 0))|, positioned = d_p < 0.05
+ *   target = base + (0.05, 0, 0), d_c = |cube - target|, d_0 = |(arm_reach + 0.1, 0, cube_size / 2) - target|
+ *   r = 2 (1 - tanh 5 d_t) + 2 g + 1.5 (1 - tanh 3 d_p) g + 3 ((d_0 - d_c) / d_0) positioned g;
+ *   cube_x > arm_reach + 0.15: r -= 2; success: r += 5; reward = r times reward_scale, metrics[2] = r / 5.
+ * (The two centres differ, 0.1 arm_reach = 0.035 against 0.05, as in the task definition.) */
+typedef struct mssim_pulltool_task {
+  int32_t tcp_row, cube_row, tool_row, base_row, finger1_row, finger2_row; /* rigid_body_data body rows */
+  float cube_half_size;       /* 0.02 */
+  float hook_length;          /* 0.05 */
+  float arm_reach;            /* 0.35 */
+  float cube_size;            /* 0.02 (sic: the task definition carries both) */
+  float pulled_close_dist;    /* 0.6  */
+  float min_force;            /* 0.5 N  (is_grasping of the tool) */
+  float max_angle_deg;        /* 20 */
+  float reward_scale;         /* 1 (dense) or 1/5 (normalized_dense) */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;
+  int32_t time_limit;
+  uint8_t* terminated_out;
+} mssim_pulltool_task;
+
+int mssim_task_pulltool_outputs(mssim_handle h, const mssim_pulltool_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream);
+
 /* How many control steps of this handle so far ran as one launch with a task epilogue at the control-step kernel's
  * tail (a deferred step_action + fetch consumed by a task_*_outputs call), against the separate epilogue launch.
  * A host counter: no sync. */

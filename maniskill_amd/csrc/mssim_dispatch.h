@@ -6,10 +6,11 @@
 
 namespace mssim_dispatch {
 
-// TASK: 0 = plain control step; else the copy-out + that task's epilogue at the kernel's tail. kRoll, kPull, kPoke
-// and kLiftPeg have no row in kTails: their epilogue is always a launch of its own, tail_step() answers kNone for them
-// (kPoke on the two-row plain step, the other three on the one-row one).
-enum Task { kPlain = 0, kPick = 1, kPush = 2, kPeg = 3, kStack = 4, kPushT = 5, kRoll = 6, kPull = 7, kPoke = 8, kLiftPeg = 9, kNumTasks = 10 };
+// TASK: 0 = plain control step; else the copy-out + that task's epilogue at the kernel's tail. kRoll, kPull, kPoke,
+// kLiftPeg, kPlace and kPullTool have no row in kTails: their epilogue is always a launch of its own, tail_step() answers
+// kNone for them (kPoke and kPullTool on the two-row plain step, the other four on the one-row one).
+enum Task { kPlain = 0, kPick = 1, kPush = 2, kPeg = 3, kStack = 4, kPushT = 5, kRoll = 6, kPull = 7, kPoke = 8, kLiftPeg = 9, kPlace = 10, kPullTool = 11,
+            kNumTasks = 12 };
 
 struct Key {
   int ndof;  // joints unrolled at compile time (9: the Panda, 7: panda_stick, 15: the Fetch), 0 = any topology

@@ -1051,6 +1051,127 @@ __global__ __launch_bounds__(256) void k_task_liftpeg(DevModel M, DevState S, ms
   task_liftpeg_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
 }
 
+// PlaceSphere evaluate / obs / reward (place_sphere.py evaluate, _get_obs_extra, compute_dense_reward, in its order of
+// overwrites): StackCube's place-and-release shape against a kinematic bin, with the robot's is_static as a third term of
+// the on-bin tier. Every sum is formed left to right as the torch path forms it (off_z - radius - bin_base_half; bin_z +
+// bin_base_half + radius). One lane per env; never at the control-step kernel's tail.
+MS_DEV void task_place_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_place_task& T, const int* __restrict__ pairs, int npairs,
+                           float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 21);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  float qv_max = 0.f;
+  for (int j = 0; j < n; j++) {
+    const float q = B.art_qpos[(size_t)e * n + j], v = B.art_qvel[(size_t)e * n + j];
+    o[j] = q;
+    o[n + j] = v;
+    if (j < T.n_static_dofs) qv_max = fmaxf(qv_max, fabsf(v));
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* ob = rowp(T.obj_row);
+  const float* bn = rowp(T.bin_row);
+  const f3 ptcp = f3{tcp[0], tcp[1], tcp[2]}, pobj = f3{ob[0], ob[1], ob[2]}, pbin = f3{bn[0], bn[1], bn[2]};
+  const bool grasped = fingers_grasp(M, S, pairs, npairs, rowp(T.finger1_row), rowp(T.finger2_row), T.min_force, T.max_angle_deg, e);
+  // evaluate
+  const f3 off = pobj - pbin;
+  const bool on = sqrtf(off.x * off.x + off.y * off.y) <= T.on_bin_tol && fabsf(off.z - T.radius - T.bin_base_half) <= T.on_bin_tol;
+  const float v = norm(f3{ob[7], ob[8], ob[9]}), av = norm(f3{ob[10], ob[11], ob[12]});
+  const bool is_static = v <= T.static_lin_thresh && av <= T.static_ang_thresh;
+  const bool success = on && is_static && !grasped;
+  // observation
+  int k = 2 * n;
+  o[k++] = grasped ? 1.f : 0.f;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  o[k++] = pbin.x; o[k++] = pbin.y; o[k++] = pbin.z;
+  for (int i = 0; i < 7; i++) o[k++] = ob[i];
+  o[k++] = pobj.x - ptcp.x; o[k++] = pobj.y - ptcp.y; o[k++] = pobj.z - ptcp.z;
+  // dense reward: each tier replaces the one before
+  float r = 2.f * (1.f - tanhf(5.f * norm(ptcp - pobj)));
+  if (grasped) r = 4.f + (1.f - tanhf(5.f * norm(f3{pbin.x, pbin.y, pbin.z + T.bin_base_half + T.radius} - pobj)));
+  if (on) {
+    const float ungrasp = grasped ? (B.art_qpos[(size_t)e * n + n - 2] + B.art_qpos[(size_t)e * n + n - 1]) / T.gripper_width : 16.f;
+    const float robot_static = qv_max <= T.robot_static_thresh ? 1.f : 0.f;
+    r = 6.f + (ungrasp + (1.f - tanhf(v * 10.f + av)) + robot_static) / 3.f;
+  }
+  if (success) r = 13.f;
+  reward[e] = r * T.reward_scale;
+  uint8_t* f = flags + 4 * (size_t)e;
+  f[0] = success; f[1] = grasped; f[2] = on; f[3] = is_static;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_place(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_place_task T, const int* __restrict__ pairs, int npairs,
+                                                     float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_place_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
+}
+
+// PullCubeTool evaluate / obs / reward (pull_cube_tool.py evaluate, _get_obs_extra, compute_dense_reward): the reward is
+// computed once, where the torch path computes it in evaluate() and again in get_reward(). The offsets are formed as the
+// torch path forms them: the Python sums in double, rounded once to float32. The per-env values of the two batch means of
+// evaluate() go to `metrics`; the means themselves are the caller's (no atomics here: the result stays deterministic).
+// One lane per env; never at the control-step kernel's tail.
+MS_DEV void task_pulltool_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_pulltool_task& T, const int* __restrict__ pairs, int npairs,
+                              float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 21);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  for (int j = 0; j < n; j++) {
+    o[j] = B.art_qpos[(size_t)e * n + j];
+    o[n + j] = B.art_qvel[(size_t)e * n + j];
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* cb = rowp(T.cube_row);
+  const float* tl = rowp(T.tool_row);
+  const float* bs = rowp(T.base_row);
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  for (int i = 0; i < 7; i++) o[k++] = cb[i];
+  for (int i = 0; i < 7; i++) o[k++] = tl[i];
+  const f3 ptcp = f3{tcp[0], tcp[1], tcp[2]}, pcube = f3{cb[0], cb[1], cb[2]}, ptool = f3{tl[0], tl[1], tl[2]}, pbase = f3{bs[0], bs[1], bs[2]};
+  const bool grasped = fingers_grasp(M, S, pairs, npairs, rowp(T.finger1_row), rowp(T.finger2_row), T.min_force, T.max_angle_deg, e);
+  // evaluate
+  const float bx = pcube.x - pbase.x, by = pcube.y - pbase.y;
+  const bool success = sqrtf(bx * bx + by * by) < T.pulled_close_dist;
+  const float to_workspace = norm(pcube - f3{pbase.x + (float)((double)T.arm_reach * 0.1), pbase.y, pbase.z});
+  const float progress = 1.f - tanhf(3.f * to_workspace);
+  // dense reward: reach the tool's handle, grasp it, bring the hook behind the cube, pull the cube in
+  const float g = grasped ? 1.f : 0.f;
+  const float tcp_to_tool = norm(ptcp - f3{ptool.x + 0.02f, ptool.y, ptool.z});
+  float r = 2.f * (1.f - tanhf(5.f * tcp_to_tool)) + 2.f * g;
+  const f3 ideal_hook = f3{pcube.x + (float)(-((double)T.hook_length + (double)T.cube_half_size)), pcube.y + -0.067f, pcube.z};
+  const float positioning_dist = norm(ptool - ideal_hook);
+  const float positioned = positioning_dist < 0.05f ? 1.f : 0.f;
+  const f3 target = f3{pbase.x + 0.05f, pbase.y, pbase.z};
+  const float cube_to_target = norm(pcube - target);
+  const float initial_dist = norm(f3{(float)((double)T.arm_reach + 0.1), 0.f, (float)((double)T.cube_size / 2)} - target);
+  r += 1.5f * (1.f - tanhf(3.f * positioning_dist)) * g;
+  r += 3.f * ((initial_dist - cube_to_target) / initial_dist) * positioned * g;
+  if (pcube.x > (float)((double)T.arm_reach + 0.15)) r -= 2.f;
+  if (success) r += 5.f;
+  reward[e] = r * T.reward_scale;
+  flags[e] = success;
+  float* m = metrics + 3 * (size_t)e;
+  m[0] = to_workspace; m[1] = progress; m[2] = r / 5.f;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_pulltool(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_pulltool_task T, const int* __restrict__ pairs, int npairs,
+                                                        float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_pulltool_env(M, S, B, T, pairs, npairs, obs, reward, flags, metrics, e);
+}
+
 // PushT pseudo-render (push_t.py pseudo_render_intersection): every template pixel (i, j) of the block's T, at its uv
 // grid centre (U[j], V[i], 1), is mapped by world_to_goal @ tee_to_world, divided by the third row, scaled to pixel
 // indices and truncated toward zero (.long()); an index outside [0, 64) sends the pixel to (0, 0). Index pair (x, y)
@@ -1763,7 +1884,7 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
   return 0;
 }
 
-// A task epilogue, the one sequence behind the nine mssim_task_*_outputs. Refusals come first and leave what is owed owed.
+// A task epilogue, the one sequence behind the eleven mssim_task_*_outputs. Refusals come first and leave what is owed owed.
 // An owed step_action + an owed fetch + the epilogue = ONE launch of the control-step kernel, where mssim_create found an
 // instance with the task's tail for the model (h->tail_fn). Otherwise what is owed is performed and the epilogue is a launch
 // of its own: `standalone(std::true_type, what, st)` launches k_task_*<true>, which first performs the owed copy-out `what`,
@@ -1789,8 +1910,8 @@ static int task_refusals(mssim_handle h, const TaskCall& c, const int (&rows)[NR
     if (int rc = finger_pair_list(h, c.pair_rows[0], c.pair_rows[1], c.pair_rows[2])) return rc;
   return 0;
 }
-// The tail-less path, for a task without a member in the tail_task union (RollBall, PullCube, PokeCube, LiftPegUpright:
-// h->tail_fn[c.id] is null for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
+// The tail-less path, for a task without a member in the tail_task union (RollBall, PullCube, PokeCube, LiftPegUpright, PlaceSphere,
+// PullCubeTool: h->tail_fn[c.id] is null for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
 template <size_t NROWS, class Standalone>
 static int task_outputs(mssim_handle h, const TaskCall& c, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
   if (int rc = task_refusals(h, c, rows)) return rc;
@@ -1921,6 +2042,30 @@ int mssim_task_liftpeg_outputs(mssim_handle h, const mssim_liftpeg_task* task, f
   return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
     hipLaunchKernelGGL(k_task_liftpeg<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
                        h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags);
+  });
+}
+
+int mssim_task_place_outputs(mssim_handle h, const mssim_place_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
+  const int rows[] = {task->tcp_row, task->obj_row, task->bin_row, task->finger1_row, task->finger2_row};
+  const int pair_rows[] = {task->obj_row, task->finger1_row, task->finger2_row};
+  const bool ok = h->M.n_dof >= 2 && task->gripper_width > 0.f;
+  const TaskCall call{mssim_dispatch::kPlace, "place", ok ? nullptr : "task_place_outputs: needs two finger joints and a gripper width > 0", pair_rows,
+                      obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    // launch shapes as mssim_task_pick_outputs
+    hipLaunchKernelGGL(k_task_place<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags);
+  });
+}
+
+int mssim_task_pulltool_outputs(mssim_handle h, const mssim_pulltool_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream) {
+  const int rows[] = {task->tcp_row, task->cube_row, task->tool_row, task->base_row, task->finger1_row, task->finger2_row};
+  const int pair_rows[] = {task->tool_row, task->finger1_row, task->finger2_row};  // (both boxes of the tool: one body row)
+  const TaskCall call{mssim_dispatch::kPullTool, "pulltool", metrics ? nullptr : "task_pulltool_outputs: needs the metrics output (device [N][3] f32)", pair_rows,
+                      obs, reward, flags, metrics};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    hipLaunchKernelGGL(k_task_pulltool<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, metrics);
   });
 }
 

@@ -1,2 +1,3 @@
-from .tabletop import LiftPegUprightEnv, PegInsertionSideEnv, PickCubeEnv, PokeCubeEnv, PullCubeEnv, PushCubeEnv, PushTEnv, RollBallEnv, StackCubeEnv
+from .tabletop import (LiftPegUprightEnv, PegInsertionSideEnv, PickCubeEnv, PlaceSphereEnv, PokeCubeEnv, PullCubeEnv, PullCubeToolEnv, PushCubeEnv, PushTEnv,
+                       RollBallEnv, StackCubeEnv)
 from .empty_env import EmptyEnv

@@ -1,0 +1,178 @@
+"""PlaceSphere-v1 (task definition restated from mani_skill/envs/tasks/tabletop/place_sphere.py:23-258):
+pick up a sphere, place it into a shallow bin and let go; success = the sphere resting in the bin (within 5 mm in xy and
+z), static and not grasped. The bin is a kinematic body of five boxes: a bottom plate and four edge blocks. As in the
+reference, the on-bin tier of the dense reward gives an ungrasped sphere 16 for its ungrasp term (so that an open gripper
+outweighs everything else there) and adds the robot's own is_static as 0 or 1."""
+from typing import Any, Dict
+
+import numpy as np
+import sapien
+import torch
+
+from maniskill_amd.envs.sapien_env import BaseEnv
+from maniskill_amd.sensors.camera import CameraConfig
+from maniskill_amd.utils import sapien_utils
+from maniskill_amd.utils.building import actors
+from maniskill_amd.utils.registration import register_env
+from maniskill_amd.utils.scene_builder.table import TableSceneBuilder
+from maniskill_amd.utils.structs.pose import Pose
+from maniskill_amd.utils.structs.types import GPUMemoryConfig, SimConfig
+
+
+@register_env("PlaceSphere-v1", max_episode_steps=50)
+class PlaceSphereEnv(BaseEnv):
+    SUPPORTED_ROBOTS = ["panda", "fetch"]
+    radius = 0.02  # the sphere's
+    inner_side_half_len = 0.02  # half the side of the bin's inner square
+    short_side_half_size = 0.0025  # half the thickness of every block of the bin
+    # half sizes along x, y, z of the edge block on the bin's -x / +x side; the bottom plate is `block_half_size` with
+    # its first entry moved to the end, the -y / +y edge blocks are `edge_block_half_size` with x and y swapped
+    block_half_size = [short_side_half_size, 2 * short_side_half_size + inner_side_half_len, 2 * short_side_half_size + inner_side_half_len]
+    edge_block_half_size = [short_side_half_size, 2 * short_side_half_size + inner_side_half_len, 2 * short_side_half_size]
+
+    def __init__(self, *args, robot_uids="panda", robot_init_qpos_noise=0.02, **kwargs):
+        self.robot_init_qpos_noise = robot_init_qpos_noise
+        super().__init__(*args, robot_uids=robot_uids, **kwargs)
+
+    @property
+    def _default_sim_config(self):
+        return SimConfig(gpu_memory_config=GPUMemoryConfig(found_lost_pairs_capacity=2**25, max_rigid_patch_count=2**18))
+
+    @property
+    def _default_sensor_configs(self):
+        pose = sapien_utils.look_at(eye=[0.3, 0, 0.2], target=[-0.1, 0, 0])
+        return [CameraConfig("base_camera", pose, 128, 128, np.pi / 2, 0.01, 100)]
+
+    @property
+    def _default_human_render_camera_configs(self):
+        pose = sapien_utils.look_at([0.6, -0.2, 0.2], [0.0, 0.0, 0.2])
+        return CameraConfig("render_camera", pose, 512, 512, 1, 0.01, 100)
+
+    def _build_bin(self):
+        """bottom plate [0.025, 0.025, 0.0025] at the origin; edge blocks at +-0.0225 in x or y, 0.0075 up"""
+        builder = self.scene.create_actor_builder()
+        b, e = self.block_half_size, self.edge_block_half_size
+        dx = dy = b[1] - b[0]
+        dz = e[2] + b[0]
+        edge_y = [e[1], e[0], e[2]]
+        for p, half in (([0, 0, 0], [b[1], b[2], b[0]]), ([-dx, 0, dz], e), ([dx, 0, dz], e), ([0, -dy, dz], edge_y), ([0, dy, dz], edge_y)):
+            builder.add_box_collision(sapien.Pose(p), half)
+            builder.add_box_visual(sapien.Pose(p), half)
+        return builder.build_kinematic(name="bin")
+
+    def _load_agent(self, options: dict):
+        super()._load_agent(options, sapien.Pose(p=[-0.615, 0, 0]))
+
+    def _load_scene(self, options: dict):
+        self._fused_state = None
+        self.table_scene = TableSceneBuilder(env=self, robot_init_qpos_noise=self.robot_init_qpos_noise)
+        self.table_scene.build()
+        self.obj = actors.build_sphere(self.scene, radius=self.radius, color=np.array([12, 42, 160, 255]) / 255, name="sphere", body_type="dynamic")
+        self.bin = self._build_bin()
+
+    def _initialize_episode(self, env_idx: torch.Tensor, options: dict):
+        dev = self.device  # explicit devices, see PickCubeEnv._initialize_episode
+        b = len(env_idx)
+        self.table_scene.initialize(env_idx)
+        # the sphere in the quarter of the workspace nearest the robot, the bin in the far half: they do not touch
+        xyz = torch.zeros((b, 3), device=dev)
+        xyz[..., 0] = (torch.rand((b, 1), device=dev) * 0.05 - 0.1)[..., 0]
+        xyz[..., 1] = (torch.rand((b, 1), device=dev) * 0.2 - 0.1)[..., 0]
+        xyz[..., 2] = self.radius
+        self.obj.set_pose(Pose.create_from_pq(p=xyz, q=[1, 0, 0, 0]))
+        pos = torch.zeros((b, 3), device=dev)
+        pos[:, 0] = torch.rand((b, 1), device=dev)[..., 0] * 0.1
+        pos[:, 1] = torch.rand((b, 1), device=dev)[..., 0] * 0.2 - 0.1
+        pos[:, 2] = self.block_half_size[0]
+        self.bin.set_pose(Pose.create_from_pq(p=pos, q=[1, 0, 0, 0]))
+
+    def evaluate(self):
+        offset = self.obj.pose.p - self.bin.pose.p
+        xy_flag = torch.linalg.norm(offset[..., :2], axis=1) <= 0.005
+        z_flag = torch.abs(offset[..., 2] - self.radius - self.block_half_size[0]) <= 0.005
+        is_obj_on_bin = torch.logical_and(xy_flag, z_flag)
+        is_obj_static = self.obj.is_static(lin_thresh=1e-2, ang_thresh=0.5)
+        is_obj_grasped = self.agent.is_grasping(self.obj)
+        success = is_obj_on_bin & is_obj_static & (~is_obj_grasped)
+        return {
+            "is_obj_grasped": is_obj_grasped,
+            "is_obj_on_bin": is_obj_on_bin,
+            "is_obj_static": is_obj_static,
+            "success": success,
+        }
+
+    def _get_obs_extra(self, info: Dict):
+        obs = dict(is_grasped=info["is_obj_grasped"], tcp_pose=self.agent.tcp.pose.raw_pose, bin_pos=self.bin.pose.p)
+        if "state" in self.obs_mode:
+            obs.update(obj_pose=self.obj.pose.raw_pose, tcp_to_obj_pos=self.obj.pose.p - self.agent.tcp.pose.p)
+        return obs
+
+    def _gripper_width(self) -> torch.Tensor:
+        """fully open finger gap, qlimits[-1].hi * 2 (Panda-specific, as in StackCube)"""
+        return (self.agent.robot.get_qlimits()[0, -1, 1] * 2).to(self.device)
+
+    def compute_dense_reward(self, obs: Any, action: torch.Tensor, info: Dict):
+        # reaching
+        obj_pos = self.obj.pose.p
+        reward = 2 * (1 - torch.tanh(5 * torch.linalg.norm(self.agent.tcp.pose.p - obj_pos, axis=1)))
+        # grasped: bring the sphere to where it rests on the bin's bottom plate
+        bin_top_pos = self.bin.pose.p.clone()
+        bin_top_pos[:, 2] = bin_top_pos[:, 2] + self.block_half_size[0] + self.radius
+        place_reward = 1 - torch.tanh(5.0 * torch.linalg.norm(bin_top_pos - obj_pos, axis=1))
+        is_obj_grasped = info["is_obj_grasped"]
+        reward[is_obj_grasped] = (4 + place_reward)[is_obj_grasped]
+        # on the bin: let go, sphere and robot at rest (16 for a released sphere: more than the other two terms can give)
+        ungrasp_reward = torch.sum(self.agent.robot.get_qpos()[:, -2:], axis=1) / self._gripper_width()
+        ungrasp_reward[~is_obj_grasped] = 16.0
+        v = torch.linalg.norm(self.obj.linear_velocity, axis=1)
+        av = torch.linalg.norm(self.obj.angular_velocity, axis=1)
+        static_reward = 1 - torch.tanh(v * 10 + av)
+        robot_static_reward = self.agent.is_static(0.2)
+        on = info["is_obj_on_bin"]
+        reward[on] = (6 + (ungrasp_reward + static_reward + robot_static_reward) / 3.0)[on]
+        reward[info["success"]] = 13
+        return reward
+
+    def compute_normalized_dense_reward(self, obs: Any, action: torch.Tensor, info: Dict):
+        return self.compute_dense_reward(obs=obs, action=action, info=info) / 13.0
+
+    # ---- fused evaluate + obs + reward (one native launch after the control step's; tests/test_gpu_place_tool.py) ----
+    def _fused_task_ok(self) -> bool:
+        cls = type(self)
+        same = all(
+            getattr(cls, m) is getattr(PlaceSphereEnv, m)
+            for m in ("evaluate", "_get_obs_extra", "compute_dense_reward", "compute_normalized_dense_reward", "_gripper_width", "_get_obs_agent", "get_obs",
+                      "get_info", "get_reward")
+        )
+        from maniskill_amd.agents.robots.panda import Panda
+        from maniskill_amd.utils.structs.actor import Actor
+
+        return (same and self.robot_uids == "panda" and type(self.agent).is_grasping is Panda.is_grasping and type(self.agent).is_static is Panda.is_static
+                and type(self.obj).is_static is Actor.is_static and self._obs_mode == "state" and self._reward_mode in ("dense", "normalized_dense")
+                and len(self.agent.controller.get_state()) == 0)
+
+    def _fused_step_outputs(self, action, advance: bool = True):
+        if not self._fused_ok():
+            return None
+        from maniskill_amd import native
+
+        px = self.scene.px
+        st = getattr(self, "_fused_state", None)
+        if st is None or st["px"] is not px:
+            task = native.PlaceTask(
+                tcp_row=self.agent.tcp._body_row, obj_row=self.obj._body_row, bin_row=self.bin._body_row,
+                finger1_row=self.agent.finger1_link._body_row, finger2_row=self.agent.finger2_link._body_row,
+                n_static_dofs=self.agent.robot.max_dof - 2, radius=self.radius, bin_base_half=self.block_half_size[0], on_bin_tol=0.005,
+                static_lin_thresh=1e-2, static_ang_thresh=0.5, robot_static_thresh=0.2, gripper_width=float(self._gripper_width()), min_force=0.5,
+                max_angle_deg=85.0, reward_scale=1.0 / 13.0 if self._reward_mode == "normalized_dense" else 1.0,
+            )
+            st = self._fused_state = dict(px=px, task=task)
+        N, D = self.num_envs, 2 * self.agent.robot.max_dof + 21
+        obs = torch.empty((N, D), dtype=torch.float32, device=self.device)
+        reward = torch.empty((N,), dtype=torch.float32, device=self.device)
+        flags = torch.empty((N, 4), dtype=torch.uint8, device=self.device)
+        es = self._fused_bind_counters(st["task"], advance)
+        px.task_place_outputs(st["task"], obs, reward, flags)
+        fb = flags.view(torch.bool)
+        info = dict(elapsed_steps=es, is_obj_grasped=fb[:, 1], is_obj_on_bin=fb[:, 2], is_obj_static=fb[:, 3], success=fb[:, 0])
+        return obs, reward, info

@@ -1,0 +1,194 @@
+"""PullCubeTool-v1 (task definition restated from mani_skill/envs/tasks/tabletop/pull_cube_tool.py:19-282):
+a cube lies out of the arm's reach; grasp an L-shaped tool (a handle and a hook, two boxes on one dynamic body) and pull
+the cube in with it. Success = the cube within 0.6 m of the robot's base link, in xy.
+The reference's quirks are kept, a learner's reward and info depend on them: `evaluate` measures the cube against base +
+(0.1 arm_reach, 0, 0) = base + (0.035, 0, 0) while the reward's target is base + (0.05, 0, 0); the reward's
+`initial_dist` is measured from a fixed world point, so it depends on where the base stands; the tool's grasp is tested
+with `max_angle=20`; the success bonus (+5) is added, not written over the staged reward, and the normalised reward is
+dense / 5, which exceeds 1; `cube_progress` and `cube_distance` are means over the batch (0-d tensors); `evaluate`
+itself returns the normalised reward as `info["reward"]`."""
+from typing import Any, Dict
+
+import numpy as np
+import sapien
+import torch
+
+from maniskill_amd.envs.sapien_env import BaseEnv
+from maniskill_amd.envs.utils import randomization
+from maniskill_amd.sensors.camera import CameraConfig
+from maniskill_amd.utils import sapien_utils
+from maniskill_amd.utils.building import actors
+from maniskill_amd.utils.registration import register_env
+from maniskill_amd.utils.scene_builder.table import TableSceneBuilder
+from maniskill_amd.utils.structs.pose import Pose
+from maniskill_amd.utils.structs.types import GPUMemoryConfig, SimConfig
+
+
+@register_env("PullCubeTool-v1", max_episode_steps=100)
+class PullCubeToolEnv(BaseEnv):
+    SUPPORTED_ROBOTS = ["panda_wristcam", "fetch"]
+    SUPPORTED_REWARD_MODES = ("normalized_dense", "dense", "sparse", "none")
+    goal_radius = 0.3
+    cube_half_size = 0.02
+    handle_length = 0.2
+    hook_length = 0.05
+    width = 0.05
+    height = 0.05
+    cube_size = 0.02
+    arm_reach = 0.35
+
+    def __init__(self, *args, robot_uids="panda_wristcam", robot_init_qpos_noise=0.02, **kwargs):
+        self.robot_init_qpos_noise = robot_init_qpos_noise
+        super().__init__(*args, robot_uids=robot_uids, **kwargs)
+
+    @property
+    def _default_sim_config(self):
+        return SimConfig(gpu_memory_config=GPUMemoryConfig(found_lost_pairs_capacity=2**25, max_rigid_patch_count=2**18))
+
+    @property
+    def _default_sensor_configs(self):
+        pose = sapien_utils.look_at(eye=[0.3, 0, 0.5], target=[-0.1, 0, 0.1])
+        return [CameraConfig("base_camera", pose, 128, 128, np.pi / 2, 0.01, 100)]
+
+    @property
+    def _default_human_render_camera_configs(self):
+        pose = sapien_utils.look_at([0.6, 0.7, 0.6], [0.0, 0.0, 0.35])
+        return CameraConfig("render_camera", pose, 512, 512, 1, 0.01, 100)
+
+    def _build_l_shaped_tool(self, handle_length, hook_length, width, height):
+        """the handle along +x from the body's origin at half the default density; the hook, twice as wide, at the
+        handle's far end on its +y side"""
+        builder = self.scene.create_actor_builder()
+        handle_p, handle_half = [handle_length / 2, 0, 0], [handle_length / 2, width / 2, height / 2]
+        hook_p, hook_half = [handle_length - hook_length / 2, width, 0], [hook_length / 2, width, height / 2]
+        builder.add_box_collision(sapien.Pose(handle_p), handle_half, density=500)
+        builder.add_box_visual(sapien.Pose(handle_p), handle_half)
+        builder.add_box_collision(sapien.Pose(hook_p), hook_half)
+        builder.add_box_visual(sapien.Pose(hook_p), hook_half)
+        return builder.build(name="l_shape_tool")
+
+    def _load_scene(self, options: dict):
+        self._fused_state = None
+        self.scene_builder = TableSceneBuilder(self, robot_init_qpos_noise=self.robot_init_qpos_noise)
+        self.scene_builder.build()
+        self.cube = actors.build_cube(self.scene, half_size=self.cube_half_size, color=np.array([12, 42, 160, 255]) / 255, name="cube", body_type="dynamic")
+        self.l_shape_tool = self._build_l_shaped_tool(handle_length=self.handle_length, hook_length=self.hook_length, width=self.width, height=self.height)
+
+    def _initialize_episode(self, env_idx: torch.Tensor, options: dict):
+        dev = self.device  # explicit devices, see PickCubeEnv._initialize_episode
+        b = len(env_idx)
+        self.scene_builder.initialize(env_idx)
+        # the tool flat on the table, within reach
+        tool_xyz = torch.zeros((b, 3), device=dev)
+        tool_xyz[..., :2] = -torch.rand((b, 2), device=dev) * 0.2 - 0.1
+        tool_xyz[..., 2] = self.height / 2
+        tool_q = torch.tensor([1, 0, 0, 0], device=dev).expand(b, 4)
+        self.l_shape_tool.set_pose(Pose.create_from_pq(p=tool_xyz, q=tool_q))
+        # the cube beyond it, turned about z by up to 30 degrees (its height as the reference writes it: 5 mm above rest)
+        cube_xyz = torch.zeros((b, 3), device=dev)
+        cube_xyz[..., 0] = self.arm_reach + torch.rand(b, device=dev) * self.handle_length - 0.3
+        cube_xyz[..., 1] = torch.rand(b, device=dev) * 0.3 - 0.25
+        cube_xyz[..., 2] = self.cube_size / 2 + 0.015
+        cube_q = randomization.random_quaternions(b, lock_x=True, lock_y=True, lock_z=False, bounds=(-np.pi / 6, np.pi / 6), device=dev)
+        self.cube.set_pose(Pose.create_from_pq(p=cube_xyz, q=cube_q))
+
+    def _get_obs_extra(self, info: Dict):
+        obs = dict(tcp_pose=self.agent.tcp.pose.raw_pose)
+        if self.obs_mode_struct.use_state:
+            obs.update(cube_pose=self.cube.pose.raw_pose, tool_pose=self.l_shape_tool.pose.raw_pose)
+        return obs
+
+    def evaluate(self):
+        cube_pos = self.cube.pose.p
+        robot_base_pos = self.agent.robot.get_links()[0].pose.p
+        cube_pulled_close = torch.linalg.norm(cube_pos[:, :2] - robot_base_pos[:, :2], dim=1) < 0.6
+        workspace_center = robot_base_pos.clone()
+        workspace_center[:, 0] += self.arm_reach * 0.1
+        cube_to_workspace_dist = torch.linalg.norm(cube_pos - workspace_center, dim=1)
+        progress = 1 - torch.tanh(3.0 * cube_to_workspace_dist)
+        return {
+            "success": cube_pulled_close,
+            "success_once": cube_pulled_close,
+            "success_at_end": cube_pulled_close,
+            "cube_progress": progress.mean(),
+            "cube_distance": cube_to_workspace_dist.mean(),
+            "reward": self.compute_normalized_dense_reward(None, None, {"success": cube_pulled_close}),
+        }
+
+    def compute_dense_reward(self, obs: Any, action: torch.Tensor, info: Dict):
+        dev = self.device
+        tcp_pos, cube_pos, tool_pos = self.agent.tcp.pose.p, self.cube.pose.p, self.l_shape_tool.pose.p
+        robot_base_pos = self.agent.robot.get_links()[0].pose.p
+        # stage 1: reach the handle 2 cm from the tool's origin, and grasp it
+        tcp_to_tool_dist = torch.linalg.norm(tcp_pos - (tool_pos + torch.tensor([0.02, 0, 0], device=dev)), dim=1)
+        reaching_reward = 2.0 * (1 - torch.tanh(5.0 * tcp_to_tool_dist))
+        is_grasping = self.agent.is_grasping(self.l_shape_tool, max_angle=20)
+        grasping_reward = 2.0 * is_grasping
+        # stage 2: the hook behind the cube
+        ideal_hook_pos = cube_pos + torch.tensor([-(self.hook_length + self.cube_half_size), -0.067, 0], device=dev)
+        tool_positioning_dist = torch.linalg.norm(tool_pos - ideal_hook_pos, dim=1)
+        positioning_reward = 1.5 * (1 - torch.tanh(3.0 * tool_positioning_dist))
+        tool_positioned = tool_positioning_dist < 0.05
+        # stage 3: the cube pulled toward a point 5 cm ahead of the base, as a fraction of a nominal starting distance
+        workspace_target = robot_base_pos + torch.tensor([0.05, 0, 0], device=dev)
+        cube_to_workspace_dist = torch.linalg.norm(cube_pos - workspace_target, dim=1)
+        initial_dist = torch.linalg.norm(torch.tensor([self.arm_reach + 0.1, 0, self.cube_size / 2], device=dev) - workspace_target, dim=1)
+        pulling_progress = (initial_dist - cube_to_workspace_dist) / initial_dist
+        pulling_reward = 3.0 * pulling_progress * tool_positioned
+        # stages 2 and 3 count only while the tool is held
+        reward = reaching_reward + grasping_reward
+        reward += positioning_reward * is_grasping
+        reward += pulling_reward * is_grasping
+        cube_pushed_away = cube_pos[:, 0] > (self.arm_reach + 0.15)
+        reward[cube_pushed_away] -= 2.0
+        if "success" in info:
+            reward[info["success"]] += 5.0
+        return reward
+
+    def compute_normalized_dense_reward(self, obs: Any, action: torch.Tensor, info: Dict):
+        return self.compute_dense_reward(obs=obs, action=action, info=info) / 5.0
+
+    # ---- fused evaluate + obs + reward (one native launch after the control step's; tests/test_gpu_place_tool.py) ----
+    def _fused_task_ok(self) -> bool:
+        cls = type(self)
+        same = all(
+            getattr(cls, m) is getattr(PullCubeToolEnv, m)
+            for m in ("evaluate", "_get_obs_extra", "compute_dense_reward", "compute_normalized_dense_reward", "_get_obs_agent", "get_obs", "get_info", "get_reward")
+        )
+        from maniskill_amd.agents.robots.panda import Panda
+
+        # (panda_wristcam: the Panda's kinematics and fingers on another mount; the camera adds nothing to the state obs)
+        return (same and self.robot_uids in ("panda", "panda_wristcam") and type(self.agent).is_grasping is Panda.is_grasping and self._obs_mode == "state"
+                and self._reward_mode in ("dense", "normalized_dense") and len(self.agent.controller.get_state()) == 0)
+
+    def _fused_step_outputs(self, action, advance: bool = True):
+        """The kernel writes the per-env values once (the torch path computes the dense reward twice per step, in
+        evaluate() and in get_reward(), each with its own is_grasping). The two batch means of the info are `.mean()`
+        over a kernel-written column: two small launches more, and a result that does not depend on the order in which
+        blocks finish, which a reduction by atomics inside the kernel would."""
+        if not self._fused_ok():
+            return None
+        from maniskill_amd import native
+
+        px = self.scene.px
+        st = getattr(self, "_fused_state", None)
+        if st is None or st["px"] is not px:
+            task = native.PullToolTask(
+                tcp_row=self.agent.tcp._body_row, cube_row=self.cube._body_row, tool_row=self.l_shape_tool._body_row,
+                base_row=self.agent.robot.get_links()[0]._body_row,
+                finger1_row=self.agent.finger1_link._body_row, finger2_row=self.agent.finger2_link._body_row,
+                cube_half_size=self.cube_half_size, hook_length=self.hook_length, arm_reach=self.arm_reach, cube_size=self.cube_size, pulled_close_dist=0.6,
+                min_force=0.5, max_angle_deg=20.0, reward_scale=0.2 if self._reward_mode == "normalized_dense" else 1.0,
+            )
+            st = self._fused_state = dict(px=px, task=task)
+        N, D = self.num_envs, 2 * self.agent.robot.max_dof + 21
+        obs = torch.empty((N, D), dtype=torch.float32, device=self.device)
+        reward = torch.empty((N,), dtype=torch.float32, device=self.device)
+        flags = torch.empty((N, 1), dtype=torch.uint8, device=self.device)
+        metrics = torch.empty((N, 3), dtype=torch.float32, device=self.device)
+        es = self._fused_bind_counters(st["task"], advance)
+        px.task_pulltool_outputs(st["task"], obs, reward, flags, metrics)
+        success = flags.view(torch.bool)[:, 0]
+        info = dict(elapsed_steps=es, success=success, success_once=success, success_at_end=success, cube_progress=metrics[:, 1].mean(),
+                    cube_distance=metrics[:, 0].mean(), reward=metrics[:, 2])
+        return obs, reward, info

@@ -198,6 +198,23 @@ class LiftPegTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class PlaceTask(C.Structure):
+    """mssim_place_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("obj_row", C.c_int32), ("bin_row", C.c_int32), ("finger1_row", C.c_int32), ("finger2_row", C.c_int32),
+                ("n_static_dofs", C.c_int32), ("radius", C.c_float), ("bin_base_half", C.c_float), ("on_bin_tol", C.c_float), ("static_lin_thresh", C.c_float),
+                ("static_ang_thresh", C.c_float), ("robot_static_thresh", C.c_float), ("gripper_width", C.c_float), ("min_force", C.c_float),
+                ("max_angle_deg", C.c_float), ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
+class PullToolTask(C.Structure):
+    """mssim_pulltool_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("cube_row", C.c_int32), ("tool_row", C.c_int32), ("base_row", C.c_int32), ("finger1_row", C.c_int32), ("finger2_row", C.c_int32),
+                ("cube_half_size", C.c_float), ("hook_length", C.c_float), ("arm_reach", C.c_float), ("cube_size", C.c_float), ("pulled_close_dist", C.c_float),
+                ("min_force", C.c_float), ("max_angle_deg", C.c_float), ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
 class EeIkMap(C.Structure):
     """mssim_ee_ik_map of include/mssim_hip_tasks.h (HIP library only)"""
     _fields_ = [("link_index", C.c_int32), ("column0", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32),
@@ -269,6 +286,8 @@ class NativeLib:
             ("task_pull_outputs", C.c_int, [H, C.POINTER(PullTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_poke_outputs", C.c_int, [H, C.POINTER(PokeTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_liftpeg_outputs", C.c_int, [H, C.POINTER(LiftPegTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_place_outputs", C.c_int, [H, C.POINTER(PlaceTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_pulltool_outputs", C.c_int, [H, C.POINTER(PullToolTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
             ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
             ("ee_ik_solve", C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -451,6 +470,16 @@ class NativeSim:
         if self.lib.task_liftpeg_outputs is None:
             raise NativeError(f"{self.lib.path} has no task_liftpeg_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.task_liftpeg_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_liftpeg_outputs")
+
+    def task_place_outputs(self, task: "PlaceTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
+        if self.lib.task_place_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_place_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_place_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_place_outputs")
+
+    def task_pulltool_outputs(self, task: "PullToolTask", obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream=None):
+        if self.lib.task_pulltool_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_pulltool_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_pulltool_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream), "task_pulltool_outputs")
 
     def tail_step_count(self) -> int:
         """control steps that ran with the task epilogue at the control-step kernel's tail (HIP library only)"""

@@ -401,6 +401,15 @@ class MssimSystem:
         """LiftPegUpright evaluate / obs / reward in one launch (include/mssim_hip_tasks.h; HIP library only)"""
         self._sim.task_liftpeg_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
 
+    def task_place_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
+        """PlaceSphere evaluate / obs / reward in one launch (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_place_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
+
+    def task_pulltool_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor, metrics: Optional[torch.Tensor]):
+        """PullCubeTool evaluate / obs / reward in one launch; metrics [N][3] f32 = cube_to_workspace_dist, its progress
+        term, dense reward / 5, required (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_pulltool_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), None if metrics is None else metrics.data_ptr(), self._stream())
+
     def tail_step_count(self) -> int:
         """control steps so far that ran as one launch with the task epilogue at the kernel's tail (HIP library only)"""
         return self._sim.tail_step_count()

@@ -62,6 +62,8 @@ for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("Pe
                  (("RollBall-v1", 4096), {}), (("PullCube-v1", 4096), {}),
                  # the same on the two-row control step (peg + cube: 21 velocity components) and on one row, both with grasp detection
                  (("PokeCube-v1", 4096), {}), (("LiftPegUpright-v1", 4096), {}),
+                 # place-and-release against a five-box kinematic bin (one row), and panda_wristcam + cube + two-box tool (two rows)
+                 (("PlaceSphere-v1", 4096), {}), (("PullCubeTool-v1", 4096), {}),
                  (("PickCube-v1", 4096), dict(sim_config=dict(control_freq=25))),  # 4 substeps (SURVEY 8d reports 5 and 4)
                  # BASELINE config 5's robot and env count: the Fetch on an empty ground, and in synthetic triangle-mesh rooms
                  (("Empty-v1", 1024), dict(robot_uids="fetch")), (("SceneManipulation-v1", 1024), dict(build_config_idxs=[i % 5 for i in range(1024)]))):
