@@ -1,5 +1,5 @@
-/* mssim_hip_tasks.h -- extras of the HIP library only (libmssim.so), outside the core ABI of mssim.h: task epilogues
- * and the iterative-IK block of the action map.
+/* mssim_hip_tasks.h -- extras of the HIP library only (libmssim.so), outside the core ABI of mssim.h: task epilogues,
+ * the iterative-IK block of the action map, and the ray caster of the camera observations.
  *
  * mssim.h is the contract both implementations export (the HIP library and the CPU oracle, every MSSIM_FN of it under
  * its own prefix). The entry points below exist in the HIP library alone: plain extern "C" symbols, bound by
@@ -276,6 +276,67 @@ int mssim_set_ee_ik_map(mssim_handle h, const mssim_ee_ik_map* map, float* targe
 /* The solve alone, with the chain and settings of the block set last: q_out = q0 with the path dofs solved. */
 int mssim_ee_ik_solve(mssim_handle h, const float* target_pose /* [N][7] */, const float* q0 /* [N][n_dof] or NULL = visible qpos */,
                       float* q_out /* [N][n_dof]; dofs off the path copied from q0 */, int32_t* iters_out /* optional [N] */, void* stream);
+
+/* ---- Ray-cast camera observations: depth, actor-level segmentation and camera-frame position --------------------
+ * A scene is the geometry of one env as the ray caster sees it: analytic shapes and convex hulls (as face planes) on
+ * rows of `rigid_body_data`, with the same optional per-env overrides as mssim_model_desc ([items][N], env fastest).
+ * All arrays of the scene are HOST arrays, read once by mssim_raycast_create. Refused there (non-zero return code and
+ * a last_error text, nothing is uploaded or launched): triangle-mesh shapes (shared or per env), a per-env CONVEX
+ * type in a slot whose shared type is not CONVEX (per-env hulls), rows / plane ranges / slots out of range.
+ * NOT detected: a slot whose shared type and per-env type are both CONVEX but whose hull differs from env to env -- the
+ * scene carries one plane range per shape, every env renders it. Callers of this entry point must make sure themselves
+ * that such a slot holds the same hull in every env (maniskill_amd/model/compile.py: raycast_scene refuses the model).
+ *
+ * Conventions. The camera pose is in the SAPIEN convention (x forward, y left, z up), relative to the env frame
+ * (mount_row < 0) or to the body of `mount_row`, whose pose the kernel reads from rigid_body_data itself. Pixel
+ * (column u, row v) casts the ray o + t dir, dir = ((u + 0.5 - cx) / fx, (v + 0.5 - cy) / fy, 1) in the OpenCV camera
+ * frame (x right, y down, z forward), not normalised: t is the z-depth. Every shape is convex; a shape's hit is its
+ * ENTRY parameter, and counts when near <= t <= min(far, 32.767) -- a shape entered in front of `near`, or holding the
+ * ray's start, gives no hit (back faces are culled), and a surface beyond the int16 millimetre range is "nothing". The
+ * pixel takes the smallest hit of the env's shapes (the first shape in scene order on an exact tie).
+ * Shapes are intersected in their own frames: plane = the half space x <= 0, box = slabs, sphere, capsule / cylinder
+ * about +x (side plus caps), convex = clip against the planes (a ray parallel to a plane and outside it misses). */
+typedef struct mssim_raycast_scene {
+  int32_t n_shape;
+  const int32_t* shape_type;     /* [n_shape] MSSIM_SHAPE_* (never MSSIM_SHAPE_TRIMESH)                                   */
+  const int32_t* shape_row;      /* [n_shape] rigid_body_data body row of the owner, -1 = fixed in the env frame          */
+  const float* shape_frame;      /* [n_shape][7] p, q(wxyz): shape frame in the body (or env) frame                       */
+  const float* shape_param;      /* [n_shape][4] as mssim_model_desc.shape_param                                          */
+  const float* shape_bound;      /* [n_shape][4] bounding sphere: centre in the BODY frame, radius; radius < 0 = unbounded */
+  const int16_t* shape_seg;      /* [n_shape] segmentation id written where the shape is hit (0 is the background's)       */
+  const int32_t* shape_planes;   /* [n_shape][2] CONVEX: first plane, plane count in `planes`; others ignored             */
+  int32_t n_plane;
+  const float* planes;           /* [n_plane][4] outward unit normal n and offset d in the shape frame, n . x <= d inside  */
+  int32_t n_env_shape;           /* per-env override slots                                                                 */
+  const int32_t* shape_env_slot; /* [n_shape] slot or -1; may be NULL when n_env_shape == 0                                */
+  const float* env_shape_frame;  /* [n_env_shape * 7][N]                                                                   */
+  const float* env_shape_param;  /* [n_env_shape * 4][N]: rows 0..2 parameters, row 3 = the env's MSSIM_SHAPE_* + 1
+                                    (MSSIM_SHAPE_NONE: the env has nothing in the slot), 0 = the shared type              */
+  const float* env_shape_bound;  /* [n_env_shape * 4][N]: centre in the BODY frame, radius                                 */
+} mssim_raycast_scene;
+
+typedef struct mssim_camera_desc {
+  int32_t width, height;
+  float fx, fy, cx, cy;          /* pinhole intrinsics in pixels                                                           */
+  float near, far;               /* 0 < near < far                                                                         */
+  int32_t mount_row;             /* -1 = the env frame, else the rigid_body_data body row the camera rides on              */
+  float pose[7];                 /* p, q(wxyz) relative to the mount; used when env_pose is NULL                           */
+  const float* env_pose;         /* optional DEVICE [N][7]: a pose per env instead; read at every render, kept by the caller */
+} mssim_camera_desc;
+
+#define MSSIM_RAYCAST_MAX_MM 32767 /* the largest depth a pixel can carry, in millimetres */
+#define MSSIM_RAYCAST_CHUNK 64     /* shapes staged on chip at a time: a scene with more is walked in chunks of this many */
+
+/* Uploads the scene and the cameras; *id names them in the calls below. Allocates: not for the step loop. */
+int mssim_raycast_create(mssim_handle h, const mssim_raycast_scene* scene, const mssim_camera_desc* cameras, int32_t n_cameras, int32_t* id);
+int mssim_raycast_destroy(mssim_handle h, int32_t id);
+/* Renders camera `camera` of every env from the bound rigid_body_data as it is (call it after fetch), on the caller's
+ * stream, without host sync or allocation.
+ * pos_seg   device int16 [N][H][W][4]: x, y, z in millimetres (truncated toward zero, saturated to int16) in the
+ *           camera's OpenGL frame (x right, y up, z backward: (x_cv t, -y_cv t, -t)), then the segmentation id;
+ *           all four are 0 where nothing is hit. One 8-byte store per pixel.
+ * depth_f32 optional device float [N][H][W]: t in metres, 0 where nothing is hit. */
+int mssim_raycast_render(mssim_handle h, int32_t id, int32_t camera, int16_t* pos_seg, float* depth_f32, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1343,6 +1343,8 @@ struct Owed {
   unsigned fetch = 0u;
 };
 
+struct RcObject;  // a ray-cast scene with its cameras (mssim_raycast.h)
+
 struct mssim_sim {
   int device = 0;
   int N = 0;
@@ -1370,6 +1372,7 @@ struct mssim_sim {
   std::vector<int*> queries;
   std::vector<int> query_n;
   std::vector<int> query_kind;
+  std::vector<std::shared_ptr<RcObject>> raycasts;  // by id; a destroyed one leaves an empty entry
   std::string err;
   int* d_act_col = nullptr; float* d_act_lo = nullptr; float* d_act_hi = nullptr; int* d_act_flags = nullptr;
   EeMap ee{-1, 0, 3, 0.f, 0.f, 0.f, 0};
@@ -2146,6 +2149,9 @@ int mssim_overflow_count(mssim_handle h, void* stream) {
 }
 
 }  // extern "C"
+
+#include "mssim_raycast_desc.h"  // what mssim_raycast_create accepts (host only)
+#include "mssim_raycast.h"       // the ray caster of the camera observations: k_raycast and the mssim_raycast_* entry points
 
 #ifdef MSSIM_PHASE_CLOCKS
 // debug builds only (not part of include/mssim.h): cycles per phase of k_solve16 summed over blocks

@@ -1,0 +1,392 @@
+// mssim_raycast.h -- the ray caster behind the depth / segmentation / position camera observations
+// (include/mssim_hip_tasks.h, mssim_raycast_*). Included by mssim_kernels.hip after mssim_sim is defined.
+//
+// One block of 256 lanes renders a 16 x 16 tile of one (env, camera); each wave owns an 8 x 8 quadrant, each lane one
+// pixel. The block first stages the env's shapes in LDS in the CAMERA's frame, MSSIM_RAYCAST_CHUNK at a time (one lane per
+// shape: body pose from rigid_body_data, per-env overrides, the camera's pose -- read once per block, not once per ray):
+// 6 x 16 B per shape, read back with one address per wave (a broadcast). Every lane then walks the staged list; a
+// shape is skipped by its bounding sphere, by the whole wave when no lane's ray meets the sphere. A hull's planes are
+// read from global memory at addresses that are the same in every lane. No atomics: one lane writes each pixel, with one
+// 8-byte store (and one 4-byte store for the float depth), so a render is deterministic.
+//
+// The arithmetic (namespace rc) is plain C++ under RC_HD, so that a host build can run it too.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#ifdef __HIPCC__
+#define RC_HD __host__ __device__ __forceinline__
+#else
+#define RC_HD inline
+#endif
+
+namespace rc {
+
+template <class T> struct V3 { T x, y, z; };
+template <class T> RC_HD V3<T> operator+(V3<T> a, V3<T> b) { return V3<T>{a.x + b.x, a.y + b.y, a.z + b.z}; }
+template <class T> RC_HD V3<T> operator-(V3<T> a, V3<T> b) { return V3<T>{a.x - b.x, a.y - b.y, a.z - b.z}; }
+template <class T> RC_HD V3<T> operator*(T s, V3<T> a) { return V3<T>{s * a.x, s * a.y, s * a.z}; }
+template <class T> RC_HD T dot(V3<T> a, V3<T> b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+using v3 = V3<float>;  // the per-ray arithmetic is float
+RC_HD v3 mk(float x, float y, float z) { return v3{x, y, z}; }
+
+// Poses are composed in double while the shapes are staged (once per block and shape, a few hundred operations), so that
+// what the rays see -- one rotation matrix and one origin per shape -- is rounded to float once, not once per link of the
+// chain camera <- mount <- env <- body <- shape.
+using real = double;
+using p3 = V3<real>;
+struct q4 { real w, x, y, z; };
+struct xf { p3 p; q4 q; };  // pose: x_parent = p + rot(q) x
+
+RC_HD q4 qnorm(q4 q) {
+  const real n = sqrt(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+  if (!(n > 0.0)) return q4{1.0, 0.0, 0.0, 0.0};
+  const real s = 1.0 / n;
+  return q4{q.w * s, q.x * s, q.y * s, q.z * s};
+}
+RC_HD q4 qmul(q4 a, q4 b) {
+  return q4{a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+            a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
+}
+RC_HD q4 qconj(q4 q) { return q4{q.w, -q.x, -q.y, -q.z}; }
+RC_HD p3 qrot(q4 q, p3 v) {  // v + 2 w (u x v) + 2 u x (u x v)
+  const p3 u{q.x, q.y, q.z};
+  const p3 c{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
+  const p3 cc{u.y * c.z - u.z * c.y, u.z * c.x - u.x * c.z, u.x * c.y - u.y * c.x};
+  return v + real(2) * (q.w * c + cc);
+}
+RC_HD xf compose(xf a, xf b) { return xf{a.p + qrot(a.q, b.p), qmul(a.q, b.q)}; }  // a o b
+RC_HD xf inverse(xf a) { const q4 c = qconj(a.q); return xf{real(-1) * qrot(c, a.p), c}; }
+RC_HD xf load_xf(const float* p, size_t stride) {
+  return xf{p3{p[0], p[stride], p[2 * stride]}, qnorm(q4{p[3 * stride], p[4 * stride], p[5 * stride], p[6 * stride]})};
+}
+
+// a staged shape: the map camera (OpenCV axes) -> shape frame as rows of a matrix plus the camera's origin in the
+// shape frame, the bounding sphere in the camera frame, type, parameters, id, plane range. 6 x 16 B.
+struct Staged {
+  float r0[3], ox, r1[3], oy, r2[3], oz;  // p_shape = (r0 . p_cv + ox, r1 . p_cv + oy, r2 . p_cv + oz)
+  float bc[3], br;                        // bounding sphere, camera (OpenCV) frame; br < 0: unbounded
+  float p[3]; int type;
+  int seg, pl0, pln, pad;
+};
+static_assert(sizeof(Staged) == 96, "Staged is six 16-byte words");
+
+// rows of the rotation matrix of q
+RC_HD void qrows(q4 q, p3* r0, p3* r1, p3* r2) {
+  const real xx = q.x * q.x, yy = q.y * q.y, zz = q.z * q.z, xy = q.x * q.y, xz = q.x * q.z, yz = q.y * q.z, wx = q.w * q.x, wy = q.w * q.y, wz = q.w * q.z;
+  *r0 = p3{1.0 - 2.0 * (yy + zz), 2.0 * (xy - wz), 2.0 * (xz + wy)};
+  *r1 = p3{2.0 * (xy + wz), 1.0 - 2.0 * (xx + zz), 2.0 * (yz - wx)};
+  *r2 = p3{2.0 * (xz - wy), 2.0 * (yz + wx), 1.0 - 2.0 * (xx + yy)};
+}
+
+// stage one shape: `cam` = env frame <- camera (SAPIEN axes), `shape` = env frame <- shape frame, bound centre `bc_env`
+// in the env frame. A SAPIEN-axes point is (z_cv, -x_cv, -y_cv) of its OpenCV coordinates.
+RC_HD Staged stage(xf cam, xf shape, p3 bc_env, float br, int type, const float* param, int seg, int pl0, int pln) {
+  const xf sc = compose(inverse(shape), cam);  // shape <- camera (SAPIEN axes)
+  p3 a0, a1, a2;
+  qrows(sc.q, &a0, &a1, &a2);
+  Staged s;
+  // columns: x_cv -> -(SAPIEN y), y_cv -> -(SAPIEN z), z_cv -> SAPIEN x
+  s.r0[0] = (float)-a0.y; s.r0[1] = (float)-a0.z; s.r0[2] = (float)a0.x; s.ox = (float)sc.p.x;
+  s.r1[0] = (float)-a1.y; s.r1[1] = (float)-a1.z; s.r1[2] = (float)a1.x; s.oy = (float)sc.p.y;
+  s.r2[0] = (float)-a2.y; s.r2[1] = (float)-a2.z; s.r2[2] = (float)a2.x; s.oz = (float)sc.p.z;
+  const xf ci = inverse(cam);
+  const p3 b = ci.p + qrot(ci.q, bc_env);  // camera, SAPIEN axes
+  s.bc[0] = (float)-b.y; s.bc[1] = (float)-b.z; s.bc[2] = (float)b.x; s.br = br;
+  s.p[0] = param[0]; s.p[1] = param[1]; s.p[2] = param[2];
+  s.type = type; s.seg = seg; s.pl0 = pl0; s.pln = pln; s.pad = 0;
+  return s;
+}
+
+constexpr float kInf = INFINITY;
+
+// the slab |x| <= h along one axis: narrows [*tin, *tout]
+RC_HD void slab(float o, float d, float h, float* tin, float* tout) {
+  if (d == 0.f) {
+    if (fabsf(o) > h) { *tin = kInf; *tout = -kInf; }
+    return;
+  }
+  const float inv = 1.f / d;
+  const float t1 = (-h - o) * inv, t2 = (h - o) * inv;
+  *tin = fmaxf(*tin, fminf(t1, t2));
+  *tout = fminf(*tout, fmaxf(t1, t2));
+}
+
+// the ball of radius r about the origin (`oc`: the ray's start relative to the centre): interval of the line oc + t d
+// inside it, from the foot of the perpendicular (well conditioned where the line passes close to the centre). With the
+// x components zeroed this is the side of a cylinder about +x.
+RC_HD void ball(v3 oc, v3 d, float r, float* tin, float* tout) {
+  const float a = dot(d, d);
+  if (a == 0.f) {  // (a ray along the axis of a cylinder: inside the side for all t, or never)
+    if (dot(oc, oc) > r * r) { *tin = kInf; *tout = -kInf; } else { *tin = -kInf; *tout = kInf; }
+    return;
+  }
+  const float tm = -dot(oc, d) / a;  // parameter of the closest point
+  const v3 l = oc + tm * d;         // closest point, relative to the centre
+  const float h2 = r * r - dot(l, l);
+  if (h2 < 0.f) { *tin = kInf; *tout = -kInf; return; }
+  const float half = sqrtf(h2 / a);
+  *tin = tm - half;
+  *tout = tm + half;
+}
+
+// [tin, tout] of a cylinder of radius r and half length h about +x
+RC_HD void cylinder(v3 o, v3 d, float r, float h, float* tin, float* tout) {
+  ball(mk(0.f, o.y, o.z), mk(0.f, d.y, d.z), r, tin, tout);
+  slab(o.x, d.x, h, tin, tout);
+}
+
+// entry parameter of the ray (o, d) into the shape, in the shape's frame; +inf: the line misses it. An entry < 0 means
+// the start is inside or the shape lies behind: the caller's `near` test drops both.
+RC_HD float enter(int type, const float* p, v3 o, v3 d, const float* __restrict__ planes, int pl0, int pln) {
+  float tin = -kInf, tout = kInf;
+  switch (type) {
+    case MSSIM_SHAPE_PLANE:  // solid: x <= 0
+      if (!(d.x < 0.f)) return kInf;
+      return -o.x / d.x;
+    case MSSIM_SHAPE_BOX:
+      slab(o.x, d.x, p[0], &tin, &tout);
+      slab(o.y, d.y, p[1], &tin, &tout);
+      slab(o.z, d.z, p[2], &tin, &tout);
+      break;
+    case MSSIM_SHAPE_SPHERE:
+      ball(o, d, p[0], &tin, &tout);
+      break;
+    case MSSIM_SHAPE_CYLINDER:
+      cylinder(o, d, p[0], p[1], &tin, &tout);
+      break;
+    case MSSIM_SHAPE_CAPSULE: {  // the union of a cylinder and two balls, itself convex: the earliest entry of the three
+      float best = kInf;
+      cylinder(o, d, p[0], p[1], &tin, &tout);
+      if (tin <= tout) best = tin;
+      for (int k = 0; k < 2; k++) {
+        const float cx = k ? p[1] : -p[1];
+        ball(mk(o.x - cx, o.y, o.z), d, p[0], &tin, &tout);
+        if (tin <= tout) best = fminf(best, tin);
+      }
+      return best;
+    }
+    case MSSIM_SHAPE_CONVEX:
+      for (int k = 0; k < pln; k++) {
+        const float* pl = planes + 4 * (size_t)(pl0 + k);
+        const v3 n = mk(pl[0], pl[1], pl[2]);
+        const float nd = dot(n, d), dist = pl[3] - dot(n, o);  // dist >= 0: the start is on the inner side
+        if (nd == 0.f) {
+          if (dist < 0.f) return kInf;
+          continue;
+        }
+        const float t = dist / nd;
+        if (nd < 0.f) tin = fmaxf(tin, t); else tout = fminf(tout, t);
+      }
+      break;
+    default:
+      return kInf;
+  }
+  return tin <= tout ? tin : kInf;
+}
+
+struct Hit { float t; int seg; };
+
+// one pixel's ray (x_cv, y_cv, 1) against staged shapes [0, n): improves `hit` (strictly smaller t only)
+RC_HD void trace(const Staged* __restrict__ sh, int n, const float* __restrict__ planes, float xcv, float ycv, float near, float tmax, bool live, Hit* hit) {
+  const float dd = xcv * xcv + ycv * ycv + 1.f;
+  for (int i = 0; i < n; i++) {
+    const Staged& s = sh[i];
+    if (s.type == MSSIM_SHAPE_NONE) continue;
+    bool need = live;
+    if (s.br >= 0.f) {  // |c x d|^2 <= r^2 |d|^2: the line passes within r of the centre
+      const float cd = s.bc[0] * xcv + s.bc[1] * ycv + s.bc[2];
+      const float cc = s.bc[0] * s.bc[0] + s.bc[1] * s.bc[1] + s.bc[2] * s.bc[2];
+      // The exact test decides, this one only saves it, so it must never reject a ray that hits: a margin of a hundredth of
+      // the radius and a millimetre, plus the float cancellation error of the left side, which grows with the distance -- a
+      // few roundings of 6e-8 on terms of size |c|^2 |d|^2, covered 30 times over by 2e-6 |c|^2 |d|^2 (at 30 m that widens
+      // a small shape's sphere by 4 cm: a few exact tests more, no hit lost).
+      const float r = 1.01f * s.br + 1e-3f;
+      need = need && (cc * dd - cd * cd <= (r * r + 2e-6f * cc) * dd);
+    }
+#ifdef __HIP_DEVICE_COMPILE__
+    if (__ballot(need) == 0ull) continue;  // the whole wave skips the shape
+#endif
+    if (need) {
+      const v3 o = mk(s.ox, s.oy, s.oz);
+      const v3 d = mk(s.r0[0] * xcv + s.r0[1] * ycv + s.r0[2], s.r1[0] * xcv + s.r1[1] * ycv + s.r1[2], s.r2[0] * xcv + s.r2[1] * ycv + s.r2[2]);
+      const float t = enter(s.type, s.p, o, d, planes, s.pl0, s.pln);
+      if (t >= near && t <= tmax && t < hit->t) { hit->t = t; hit->seg = s.seg; }
+    }
+  }
+}
+
+RC_HD int mm(float metres) {  // truncated toward zero, saturated to int16
+  const float v = fminf(fmaxf(1000.f * metres, -32768.f), 32767.f);
+  return (int)v;
+}
+
+}  // namespace rc
+
+#ifdef __HIPCC__
+
+// device tables of one scene (uploaded by mssim_raycast_create)
+struct RcTables {
+  int n_shape;
+  const int* type; const int* row; const float* frame; const float* param; const float* bound; const int* seg; const int* planes2;
+  const float* plane;
+  const int* env_slot; const float* env_frame; const float* env_param; const float* env_bound;  // env_slot null: no overrides
+};
+
+struct RcCamera {
+  int width, height; float fx, fy, cx, cy, near, tmax; int mount_row; float pose[7]; const float* env_pose;
+};
+
+struct RcObject {
+  RcTables T{};
+  std::vector<RcCamera> cams;
+  std::vector<void*> allocs;
+  bool needs_rows = false;  // some shape or camera rides on a body row
+  ~RcObject() { for (void* p : allocs) (void)hipFree(p); }
+};
+
+constexpr int RC_TILE = 16;
+
+__global__ __launch_bounds__(256) void k_raycast(RcTables T, RcCamera C, const float* __restrict__ rigid, int N, int tiles_x, int tiles,
+                                                 short* __restrict__ pos_seg, float* __restrict__ depth) {
+  __shared__ __attribute__((aligned(16))) rc::Staged sh[MSSIM_RAYCAST_CHUNK];
+  const int env = blockIdx.x / tiles, tile = blockIdx.x - env * tiles;
+  if (env >= N) return;  // (never: the grid is N * tiles)
+  const int tx = tile % tiles_x, ty = tile / tiles_x;
+  // wave w owns quadrant (w & 1, w >> 1) of the tile, lane l pixel (l & 7, l >> 3) of the quadrant
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int u = tx * RC_TILE + (w & 1) * 8 + (l & 7), v = ty * RC_TILE + (w >> 1) * 8 + (l >> 3);
+  const bool live = u < C.width && v < C.height;
+  const float xcv = ((float)u + 0.5f - C.cx) / C.fx, ycv = ((float)v + 0.5f - C.cy) / C.fy;
+  rc::Hit hit{rc::kInf, 0};
+
+  for (int base = 0; base < T.n_shape; base += MSSIM_RAYCAST_CHUNK) {
+    const int n = min(MSSIM_RAYCAST_CHUNK, T.n_shape - base);
+    if (base) __syncthreads();  // the previous chunk has been walked by every wave
+    if ((int)threadIdx.x < n) {
+      const int i = base + threadIdx.x;
+      // the camera in the env frame: its mount's pose (the body row, read here) o its local pose
+      rc::xf cam = C.env_pose ? rc::load_xf(C.env_pose + 7 * (size_t)env, 1) : rc::load_xf(C.pose, 1);
+      if (C.mount_row >= 0) cam = rc::compose(rc::load_xf(rigid + ((size_t)C.mount_row * N + env) * 13, 1), cam);
+      int type = T.type[i];
+      rc::xf frame = rc::load_xf(T.frame + 7 * (size_t)i, 1);
+      float param[3] = {T.param[4 * i], T.param[4 * i + 1], T.param[4 * i + 2]};
+      rc::p3 bc{T.bound[4 * i], T.bound[4 * i + 1], T.bound[4 * i + 2]};
+      float br = T.bound[4 * i + 3];
+      const int slot = T.env_slot ? T.env_slot[i] : -1;
+      if (slot >= 0) {  // [items][N], env fastest
+        frame = rc::load_xf(T.env_frame + (size_t)slot * 7 * N + env, (size_t)N);
+        const float* ep = T.env_param + (size_t)slot * 4 * N + env;
+        const float* eb = T.env_bound + (size_t)slot * 4 * N + env;
+        const int t1 = (int)ep[3 * (size_t)N];
+        if (t1 > 0) type = t1 - 1;
+        if (type != MSSIM_SHAPE_CONVEX) { param[0] = ep[0]; param[1] = ep[(size_t)N]; param[2] = ep[2 * (size_t)N]; }
+        bc = rc::p3{eb[0], eb[(size_t)N], eb[2 * (size_t)N]};
+        br = eb[3 * (size_t)N];
+      }
+      const int row = T.row[i];
+      if (row >= 0) {
+        const rc::xf body = rc::load_xf(rigid + ((size_t)row * N + env) * 13, 1);
+        frame = rc::compose(body, frame);
+        bc = body.p + rc::qrot(body.q, bc);
+      }
+      sh[threadIdx.x] = rc::stage(cam, frame, bc, br, type, param, T.seg[i], T.planes2[2 * i], T.planes2[2 * i + 1]);
+    }
+    __syncthreads();
+    rc::trace(sh, n, T.plane, xcv, ycv, C.near, C.tmax, live, &hit);
+  }
+  if (!live) return;
+  const bool any = hit.t < rc::kInf;
+  const float t = any ? hit.t : 0.f;
+  const size_t pix = ((size_t)env * C.height + v) * C.width + u;
+  const int x = rc::mm(xcv * t), y = rc::mm(-(ycv * t)), z = rc::mm(-t);
+  uint2 out;
+  out.x = any ? ((unsigned)x & 0xffffu) | ((unsigned)y << 16) : 0u;
+  out.y = any ? ((unsigned)z & 0xffffu) | ((unsigned)hit.seg << 16) : 0u;
+  *reinterpret_cast<uint2*>(pos_seg + 4 * pix) = out;  // (hipMalloc'd / torch tensors: [N][H][W][4] int16 is 8-byte aligned per pixel)
+  if (depth) depth[pix] = t;
+}
+
+template <typename Tt>
+static int rc_upload(mssim_handle h, RcObject* o, const Tt* src, size_t count, const Tt** dst) {
+  void* d = nullptr;
+  HIPCHK(h, hipMalloc(&d, (count > 0 ? count : 1) * sizeof(Tt)));
+  o->allocs.push_back(d);
+  if (count > 0) HIPCHK(h, hipMemcpy(d, src, count * sizeof(Tt), hipMemcpyHostToDevice));
+  *dst = (const Tt*)d;
+  return 0;
+}
+
+extern "C" {
+
+int mssim_raycast_create(mssim_handle h, const mssim_raycast_scene* s, const mssim_camera_desc* cameras, int32_t n_cameras, int32_t* id) {
+  if (!h) return 1;
+  if (!id) { h->err = "raycast_create: no id"; return 1; }
+  const int N = h->N, n_rows = h->M.n_link + h->M.n_free + h->M.n_kin;
+  if (int rc = mssim_raycast::validate(s, cameras, n_cameras, N, n_rows, &h->err)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  auto o = std::make_shared<RcObject>();
+  const size_t n = (size_t)s->n_shape;
+  std::vector<int> seg(n);
+  for (size_t i = 0; i < n; i++) {
+    seg[i] = (int)(uint16_t)s->shape_seg[i];
+    o->needs_rows = o->needs_rows || s->shape_row[i] >= 0;
+  }
+  RcTables& T = o->T;
+  T.n_shape = s->n_shape;
+  if (int rc = rc_upload(h, o.get(), s->shape_type, n, &T.type)) return rc;
+  if (int rc = rc_upload(h, o.get(), s->shape_row, n, &T.row)) return rc;
+  if (int rc = rc_upload(h, o.get(), s->shape_frame, 7 * n, &T.frame)) return rc;
+  if (int rc = rc_upload(h, o.get(), s->shape_param, 4 * n, &T.param)) return rc;
+  if (int rc = rc_upload(h, o.get(), s->shape_bound, 4 * n, &T.bound)) return rc;
+  if (int rc = rc_upload(h, o.get(), seg.data(), n, &T.seg)) return rc;
+  if (int rc = rc_upload(h, o.get(), s->shape_planes, 2 * n, &T.planes2)) return rc;
+  if (int rc = rc_upload(h, o.get(), s->planes, 4 * (size_t)s->n_plane, &T.plane)) return rc;
+  if (s->n_env_shape > 0) {
+    const size_t ne = (size_t)s->n_env_shape * (size_t)N;
+    if (int rc = rc_upload(h, o.get(), s->shape_env_slot, n, &T.env_slot)) return rc;
+    if (int rc = rc_upload(h, o.get(), s->env_shape_frame, 7 * ne, &T.env_frame)) return rc;
+    if (int rc = rc_upload(h, o.get(), s->env_shape_param, 4 * ne, &T.env_param)) return rc;
+    if (int rc = rc_upload(h, o.get(), s->env_shape_bound, 4 * ne, &T.env_bound)) return rc;
+  }
+  for (int c = 0; c < n_cameras; c++) {
+    const mssim_camera_desc& k = cameras[c];
+    RcCamera cam{k.width, k.height, k.fx, k.fy, k.cx, k.cy, k.near, fminf(k.far, 0.001f * (float)MSSIM_RAYCAST_MAX_MM), k.mount_row, {}, k.env_pose};
+    for (int j = 0; j < 7; j++) cam.pose[j] = k.pose[j];
+    o->needs_rows = o->needs_rows || k.mount_row >= 0;
+    o->cams.push_back(cam);
+  }
+  h->raycasts.push_back(o);
+  *id = (int)h->raycasts.size() - 1;
+  return 0;
+}
+
+int mssim_raycast_destroy(mssim_handle h, int32_t id) {
+  if (!h) return 1;
+  if (id < 0 || id >= (int)h->raycasts.size() || !h->raycasts[id]) { h->err = "raycast_destroy: bad id"; return 1; }
+  (void)hipSetDevice(h->device);
+  h->raycasts[id].reset();
+  return 0;
+}
+
+int mssim_raycast_render(mssim_handle h, int32_t id, int32_t camera, int16_t* pos_seg, float* depth_f32, void* stream) {
+  if (!h) return 1;
+  settle(h, (hipStream_t)stream);
+  if (id < 0 || id >= (int)h->raycasts.size() || !h->raycasts[id]) { h->err = "raycast_render: bad id"; return 1; }
+  const RcObject& o = *h->raycasts[id];
+  if (camera < 0 || camera >= (int)o.cams.size()) { h->err = "raycast_render: bad camera index"; return 1; }
+  if (!pos_seg) { h->err = "raycast_render: no pos_seg output"; return 1; }
+  if (((uintptr_t)pos_seg & 7u) || ((uintptr_t)depth_f32 & 3u)) { h->err = "raycast_render: pos_seg must be 8-byte aligned, depth_f32 4-byte"; return 1; }
+  if (o.needs_rows && !h->buf.rigid_body_data) { h->err = "raycast_render: no rigid_body_data bound"; return 1; }
+  const RcCamera& C = o.cams[camera];
+  const int tiles_x = (C.width + RC_TILE - 1) / RC_TILE, tiles = tiles_x * ((C.height + RC_TILE - 1) / RC_TILE);
+  hipLaunchKernelGGL(k_raycast, dim3((unsigned)(tiles * h->N)), dim3(256), 0, (hipStream_t)stream, o.T, C, h->buf.rigid_body_data, h->N, tiles_x, tiles,
+                     (short*)pos_seg, depth_f32);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"
+
+#endif  // __HIPCC__

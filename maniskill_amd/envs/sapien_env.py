@@ -6,10 +6,13 @@ API counterpart of mani_skill/envs/sapien_env.py (constructor :185-327, reset :7
   * one batched scene, no per-env sub-scenes, always the tensor ("GPU sim") code path;
   * when neither the task nor the controller needs per-substep hooks, the
     `sim_freq // control_freq` substeps of one control step are issued as ONE native call;
-  * no renderer: obs modes are "state", "state_dict", "none".
+  * no rasteriser: the cameras cast rays at the collision geometry (maniskill_amd/sensors/camera.py). Obs modes are
+    "state", "state_dict", "none", and "depth" / "segmentation" / "position" in any "+" combination, also with
+    "state" or "state_dict"; colour ("rgb", "rgbd", "pointcloud", ...) and `render()` are not available.
 """
 import copy
 import gc
+import itertools
 from functools import cached_property
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -21,7 +24,7 @@ from gymnasium.vector.utils import batch_space
 from maniskill_amd.agents import REGISTERED_AGENTS
 from maniskill_amd.agents.base_agent import BaseAgent
 from maniskill_amd.envs.scene import ManiSkillScene
-from maniskill_amd.envs.utils.observations import parse_obs_mode_to_struct
+from maniskill_amd.envs.utils.observations import RAYCAST_TEXTURES, is_raycast_obs_mode, parse_obs_mode_to_struct
 from maniskill_amd.envs.utils.randomization.batched_rng import BatchedRNG
 from maniskill_amd.envs.utils.system.backend import CPU_SIM_BACKENDS, parse_sim_and_render_backend
 from maniskill_amd.utils import common, gym_utils
@@ -30,11 +33,23 @@ from maniskill_amd.utils.structs.articulation import Articulation
 from maniskill_amd.utils.structs.pose import Pose
 from maniskill_amd import physx
 from maniskill_amd.utils.structs.types import SimConfig, strict_from_dict
+from maniskill_amd.sensors.camera import Camera, RaycastRig, apply_sensor_overrides, camera_observations_to_images, cameras_by_uid
+
+# the camera modes in one spelling each (textures in RAYCAST_TEXTURES order, a state form last); `is_raycast_obs_mode`
+# accepts the other orders too
+_VISUAL_OBS_MODES = tuple(
+    "+".join(tex + extra)
+    for k in range(1, len(RAYCAST_TEXTURES) + 1)
+    for tex in itertools.combinations(RAYCAST_TEXTURES, k)
+    for extra in ((), ("state",), ("state_dict",))
+)
+_NO_COLOUR = (" (the cameras of this build cast rays at the collision geometry: depth, segmentation and position are available; colour -- rgb, rgbd, "
+              "pointcloud, sensor_data, normal, albedo -- is what is missing)")
 
 
 class BaseEnv(gym.Env):
     SUPPORTED_ROBOTS: List[Union[str, Tuple[str]]] = None
-    SUPPORTED_OBS_MODES = ("state", "state_dict", "none")
+    SUPPORTED_OBS_MODES = ("state", "state_dict", "none") + _VISUAL_OBS_MODES
     SUPPORTED_REWARD_MODES = ("normalized_dense", "dense", "sparse", "none")
     SUPPORTED_RENDER_MODES = ("human", "rgb_array", "sensors", "all")
     metadata = {"render_modes": SUPPORTED_RENDER_MODES}
@@ -121,7 +136,14 @@ class BaseEnv(gym.Env):
                 raise NotImplementedError(f"Unsupported {what} mode: {mode}. Must be one of {supported}{note}")
             return mode
 
-        self._obs_mode = choose(obs_mode, self.SUPPORTED_OBS_MODES, "obs", " (this build has no renderer: state observations only)")
+        # (a camera mode in any order of its parts, for an env class that lists camera modes at all)
+        if obs_mode is not None and is_raycast_obs_mode(obs_mode) and any(is_raycast_obs_mode(m) for m in self.SUPPORTED_OBS_MODES):
+            self._obs_mode = obs_mode
+        elif obs_mode is None or obs_mode in ("state", "state_dict", "none"):
+            self._obs_mode = choose(obs_mode, self.SUPPORTED_OBS_MODES, "obs")
+        else:
+            raise NotImplementedError(f"Unsupported obs mode: {obs_mode}. Must be state, state_dict, none, or one or more of {' / '.join(RAYCAST_TEXTURES)} "
+                                      f"joined by '+', optionally with state or state_dict{_NO_COLOUR}")
         self.obs_mode_struct = parse_obs_mode_to_struct(self._obs_mode)
         self._reward_mode = choose(reward_mode, self.SUPPORTED_REWARD_MODES, "reward")
 
@@ -131,6 +153,7 @@ class BaseEnv(gym.Env):
             raise NotImplementedError("Multiple controllers are not supported yet.")
         self.render_mode = render_mode
         self._sensors = dict()
+        self._custom_sensor_configs = sensor_configs
 
         self._main_seed = None
         from maniskill_amd.distributed import env_index_offset
@@ -209,9 +232,33 @@ class BaseEnv(gym.Env):
         pass
 
     def _setup_sensors(self, options: dict):
-        """cameras degrade to "none" in this build"""
+        """the task's cameras and the robot's, with the user's `sensor_configs` overrides (sapien_env.py:694-760 of the
+        reference); all of them share one native ray-cast scene, created at the first capture"""
+        self._sensor_configs = cameras_by_uid(self._default_sensor_configs)
+        self._agent_sensor_configs = cameras_by_uid(self.agent._sensor_configs) if self.agent is not None else dict()
+        self._sensor_configs.update(self._agent_sensor_configs)
+        if self._custom_sensor_configs is not None:
+            apply_sensor_overrides(self._sensor_configs, self._custom_sensor_configs)
+        self.__dict__.pop("segmentation_id_map", None)
+        rig = RaycastRig(self.scene, self._segmentation_ids_by_owner())
         self._sensors = dict()
-        self._sensor_configs = dict()
+        for uid, config in self._sensor_configs.items():
+            self._sensors[uid] = Camera(config, self.scene, self.agent.robot if uid in self._agent_sensor_configs else None, rig=rig)
+        self.scene.sensors = self._sensors
+
+    def _segmentation_ids_by_owner(self) -> Dict[str, int]:
+        """the compiled model's shape owner names (an actor's body row name, a link's name) -> segmentation id"""
+        return {getattr(o, "_row_name", None) or o.name: i for i, o in self.segmentation_id_map.items()}
+
+    @cached_property
+    def segmentation_id_map(self) -> Dict[int, Union[Actor, Any]]:
+        """segmentation id (`per_scene_id`; 0 is the background) -> the Actor or Link that carries it"""
+        structs = list(self.scene.actors.values()) + [link for art in self.scene.articulations.values() for link in art.links]
+        # (actors that share a body row across sub-scenes share an id: the first one built stands for the row)
+        by_id: Dict[int, Any] = {}
+        for struct in sorted(structs, key=lambda o: o._per_scene_id):
+            by_id.setdefault(struct._per_scene_id, struct)
+        return by_id
 
     def _after_reconfigure(self, options):
         pass
@@ -233,12 +280,44 @@ class BaseEnv(gym.Env):
         mode = self._obs_mode
         if mode == "none":
             return {}
+        info = self.get_info() if info is None else info
+        if is_raycast_obs_mode(mode):
+            obs = self._get_obs_with_sensor_data(info)
+            if self.obs_mode_struct.state:  # the flattened state replaces agent / extra
+                data = dict(agent=obs.pop("agent"), extra=obs.pop("extra"))
+                obs["state"] = common.flatten_state_dict(data, use_torch=True, device=self.device)
+            return obs
         if mode not in ("state", "state_dict"):
-            raise NotImplementedError(mode)
-        nested = self._get_obs_state_dict(self.get_info() if info is None else info)
+            raise NotImplementedError(mode + _NO_COLOUR)
+        nested = self._get_obs_state_dict(info)
         if mode == "state":
             return common.flatten_state_dict(nested, use_torch=True, device=self.device)
         return common.torch_clone_dict(nested)  # (getters are views of the simulation buffers in this build: hand out copies)
+
+    def _get_obs_with_sensor_data(self, info: Dict) -> dict:
+        state = common.torch_clone_dict(self._get_obs_state_dict(info))
+        return dict(agent=state["agent"], extra=state["extra"], sensor_param=self.get_sensor_params(), sensor_data=self._get_obs_sensor_data())
+
+    def capture_sensor_data(self):
+        """one ray-cast launch per camera on the current stream, from the fetched poses"""
+        for sensor in self._sensors.values():
+            sensor.capture()
+
+    def _get_obs_sensor_data(self) -> dict:
+        """capture, then every camera's images of the modalities the obs mode names (depth alone in the state modes, as
+        the reference renders for debugging). The tensors are views of each camera's one buffer."""
+        self.capture_sensor_data()
+        tex = self.obs_mode_struct.visual
+        if self._obs_mode in ("state", "state_dict"):
+            return {uid: cam.get_obs(depth=True, position=False, segmentation=False) for uid, cam in self._sensors.items()}
+        return {uid: cam.get_obs(depth=tex.depth, position=tex.position, segmentation=tex.segmentation) for uid, cam in self._sensors.items()}
+
+    def get_sensor_params(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        return {uid: cam.get_params() for uid, cam in self._sensors.items()}
+
+    def get_sensor_images(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        """uint8 pictures of what the cameras sense now, in the reference's depth / segmentation colourings"""
+        return {uid: camera_observations_to_images(data) for uid, data in self._get_obs_sensor_data().items()}
 
     def _get_obs_state_dict(self, info: Dict):
         return dict(agent=self._get_obs_agent(), extra=self._get_obs_extra(info))
@@ -599,7 +678,8 @@ class BaseEnv(gym.Env):
         hidden = any(getattr(o, "hidden", False) for o in self._hidden_objects)
         key = (id(self.scene), id(ctrl), getattr(self.agent, "control_mode", None), hidden)
         if self.__dict__.get("_fused_ok_key") != key:
-            self._fused_ok_key, self._fused_ok_val = key, (not hidden) and bool(self._fused_task_ok())
+            # (a visual mode takes the torch evaluate / reward path: the epilogues produce the flat state observation only)
+            self._fused_ok_key, self._fused_ok_val = key, (not hidden) and not is_raycast_obs_mode(self._obs_mode) and bool(self._fused_task_ok())
         return self._fused_ok_val
 
     def _fused_task_ok(self) -> bool:
@@ -677,7 +757,8 @@ class BaseEnv(gym.Env):
 
     # ------------------------------------------------------------------ misc
     def render(self):
-        raise NotImplementedError("rendering is out of scope of this build (state observations only)")
+        raise NotImplementedError("render() needs colour, which this build lacks: its cameras cast rays at the collision geometry (obs modes depth / "
+                                  "segmentation / position; get_sensor_images() for pictures of those)")
 
     def print_sim_details(self):
         print("# -------------------------------------------------------------------------- #")

@@ -38,6 +38,7 @@ class ManiSkillScene:
         self.human_render_cameras = {}
         self._builder = SceneModelBuilder()
         self._fragments: Dict[str, Actor] = {}  # per-env actor fragments waiting for Actor.merge
+        self._per_scene_id_next = 1  # segmentation ids of actors and links, in build order; 0 is the background
         self._gpu_sim_initialized = False
         self._needs_fetch = False
         self._all_env_idx = torch.arange(self.num_envs, device=self.device)
@@ -110,6 +111,12 @@ class ManiSkillScene:
     @timestep.setter
     def timestep(self, dt):
         self.px.timestep = dt
+
+    def _new_per_scene_id(self) -> int:
+        """the next segmentation id (`Actor.per_scene_id` / `Link.per_scene_id`): unique within an env, >= 1"""
+        i = self._per_scene_id_next
+        self._per_scene_id_next += 1
+        return i
 
     # ------------------------------------------------------------------ builders
     def create_actor_builder(self) -> ActorBuilder:

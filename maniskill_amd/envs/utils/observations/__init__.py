@@ -1,5 +1,6 @@
 """obs-mode string parsing (counterpart of mani_skill/envs/utils/observations/__init__.py:37).
-Only state modes can be produced by this build; visual textures parse but cannot be rendered."""
+This build produces the state modes and the geometric camera textures (RAYCAST_TEXTURES); the colour textures parse but
+cannot be rendered."""
 from dataclasses import dataclass
 
 ALL_VISUAL_TEXTURES = ["rgb", "depth", "segmentation", "position", "normal", "albedo"]
@@ -42,3 +43,15 @@ def parse_obs_mode_to_struct(obs_mode: str) -> ObservationModeStruct:
     return ObservationModeStruct(
         "state_dict" in tex, "state" in tex, CameraObsTextures(**{t: True for t in tex if t in ALL_VISUAL_TEXTURES})
     )
+
+
+RAYCAST_TEXTURES = ("depth", "segmentation", "position")  # what the ray-cast cameras render
+
+
+def is_raycast_obs_mode(obs_mode: str) -> bool:
+    """a camera mode this build renders: "+"-joined, in any order and without repeats, one or more of RAYCAST_TEXTURES and
+    at most one of "state" / "state_dict" """
+    parts = obs_mode.split("+")
+    textures = [t for t in parts if t in RAYCAST_TEXTURES]
+    state_forms = [t for t in parts if t in ("state", "state_dict")]
+    return len(set(parts)) == len(parts) and len(textures) + len(state_forms) == len(parts) and len(textures) >= 1 and len(state_forms) <= 1

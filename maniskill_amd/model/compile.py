@@ -654,3 +654,52 @@ class SceneModelBuilder:
             shape_owner=[s["owner"] for s in shapes],
             n_rows=n_link + n_free + n_kin,
         )
+
+
+def raycast_scene(model: CompiledModel, seg_ids: Dict[str, int]) -> Dict[str, np.ndarray]:
+    """The ray caster's view of a compiled model (`mssim_raycast_scene`, include/mssim_hip_tasks.h): every collision
+    shape with its body row, hull face planes instead of hull vertices, bounding spheres about a centre in the BODY
+    frame, and a segmentation id per shape from `seg_ids` (owner name -> id >= 1; shapes of owners it does not name get
+    0, the background's). Per-env overrides are passed on as the model holds them. Raises ValueError for what the ray
+    caster leaves out: triangle meshes and hulls that differ from env to env."""
+    A, N = model.arrays, int(model.scalars["num_envs"])
+    ns = int(model.scalars["n_shape"])
+    types, slots = A["shape_type"], A["shape_env_slot"]
+    n_es = int(model.scalars["n_env_shape"])
+    env_param = A["env_shape_param"].reshape(n_es, 4, -1) if n_es else np.zeros((0, 4, N), dtype=np.float32)
+    bound = np.zeros((ns, 4), dtype=np.float32)
+    planes, ranges, seg = [], np.zeros((ns, 2), dtype=np.int32), np.zeros(ns, dtype=np.int16)
+    for i in range(ns):
+        owner = model.shape_owner[i]
+        env_types = {int(types[i])} if slots[i] < 0 else {int(t) - 1 if t > 0 else int(types[i]) for t in np.unique(env_param[slots[i], 3])}
+        if SHAPE_TRIMESH in env_types:
+            raise ValueError(f"{owner}: triangle-mesh shapes are out of scope of the ray caster (state observations only for this scene)")
+        if SHAPE_CONVEX in env_types:
+            first, count = (int(x) for x in A["shape_hull"][i])
+            if slots[i] >= 0:
+                e = env_param[slots[i]]
+                own = e[3] == SHAPE_CONVEX + 1
+                if types[i] != SHAPE_CONVEX or np.any(e[0][own] != first) or np.any(e[1][own] != count):
+                    raise ValueError(f"{owner}: hulls that differ from env to env are out of scope of the ray caster")
+            p = mesh.hull_face_planes(np.asarray(A["hull_verts"][first : first + count], dtype=np.float64))
+            ranges[i] = (len(planes), len(p))
+            planes.extend(p.tolist())
+        c, r = A["shape_bound"][i, :3].astype(np.float64), float(A["shape_bound"][i, 3])
+        bound[i, :3] = geom.transform_point(A["shape_frame"][i].astype(np.float64), c) if r >= 0 else 0.0
+        bound[i, 3] = r
+        seg[i] = int(seg_ids.get(owner, 0))
+    return dict(
+        shape_type=np.ascontiguousarray(types, dtype=np.int32),
+        shape_row=np.ascontiguousarray(A["shape_row"], dtype=np.int32),
+        shape_frame=np.ascontiguousarray(A["shape_frame"], dtype=np.float32),
+        shape_param=np.ascontiguousarray(A["shape_param"], dtype=np.float32),
+        shape_bound=bound,
+        shape_seg=seg,
+        shape_planes=ranges,
+        planes=np.asarray(planes, dtype=np.float32).reshape(-1, 4),
+        n_env_shape=n_es,
+        shape_env_slot=np.ascontiguousarray(slots, dtype=np.int32),
+        env_shape_frame=A["env_shape_frame"],
+        env_shape_param=A["env_shape_param"],
+        env_shape_bound=A["env_shape_bound"],
+    )

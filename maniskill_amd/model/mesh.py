@@ -154,6 +154,26 @@ def hull_volume_com_inertia(verts: np.ndarray):
     return vol, com + c0, I
 
 
+def hull_face_planes(verts: np.ndarray, cos_tol: float = 1e-9, dist_tol: float = 1e-9) -> np.ndarray:
+    """[P, 4] face planes (outward unit normal n, offset d; n . x <= d inside) of conv(verts), coplanar facets merged:
+    Qhull's triangles of one face share a plane up to rounding (a cube's 12 triangles give 6 planes). `dist_tol` is
+    relative to the hull's extent. Each plane's offset is the largest n . v over the vertices, so that every vertex
+    satisfies every plane. Deterministic: planes come in the order of their first facet."""
+    v = np.asarray(verts, dtype=np.float64)
+    hull = ConvexHull(v)
+    scale = max(float(np.abs(v - v.mean(axis=0)).max()), 1e-30)
+    planes = []
+    for eq in hull.equations:
+        n = eq[:3] / np.linalg.norm(eq[:3])
+        d = -eq[3] / np.linalg.norm(eq[:3])
+        if any(np.dot(n, p[:3]) >= 1.0 - cos_tol and abs(d - p[3]) <= dist_tol * scale for p in planes):
+            continue
+        planes.append(np.array([*n, d]))
+    out = np.asarray(planes, dtype=np.float64).reshape(-1, 4)
+    out[:, 3] = (v @ out[:, :3].T).max(axis=0)
+    return out
+
+
 def simplify_hull(verts: np.ndarray, max_verts: int) -> np.ndarray:
     """Reduce a convex point set to at most `max_verts` hull vertices.
 

@@ -222,6 +222,36 @@ class EeIkMap(C.Structure):
                 ("max_iters", C.c_int32), ("damping", C.c_float), ("max_step", C.c_float), ("tolerance", C.c_float)]
 
 
+_I16P = C.POINTER(C.c_int16)
+
+
+class RaycastScene(C.Structure):
+    """mssim_raycast_scene of include/mssim_hip_tasks.h (HIP library only): host arrays, read once by raycast_create"""
+    _fields_ = [("n_shape", C.c_int32), ("shape_type", _I32P), ("shape_row", _I32P), ("shape_frame", _F32P), ("shape_param", _F32P),
+                ("shape_bound", _F32P), ("shape_seg", _I16P), ("shape_planes", _I32P), ("n_plane", C.c_int32), ("planes", _F32P),
+                ("n_env_shape", C.c_int32), ("shape_env_slot", _I32P), ("env_shape_frame", _F32P), ("env_shape_param", _F32P),
+                ("env_shape_bound", _F32P)]
+
+
+class CameraDesc(C.Structure):
+    """mssim_camera_desc of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near", C.c_float), ("far", C.c_float), ("mount_row", C.c_int32), ("pose", C.c_float * 7), ("env_pose", C.c_void_p)]
+
+
+def make_raycast_scene(arrays: dict):
+    """Returns (RaycastScene, keepalive) from the arrays of `model.compile.raycast_scene` (or hand-made ones with the
+    same keys); keepalive must outlive the create call."""
+    d, keep = RaycastScene(), []
+    d.n_shape, d.n_plane, d.n_env_shape = len(arrays["shape_type"]), len(arrays["planes"]), int(arrays.get("n_env_shape", 0))
+    for name, ctype in RaycastScene._fields_:
+        if ctype in (_I32P, _F32P, _I16P):
+            a = np.ascontiguousarray(arrays[name], dtype={_I32P: np.int32, _F32P: np.float32, _I16P: np.int16}[ctype])
+            keep.append(a)
+            setattr(d, name, a.ctypes.data_as(ctype))
+    return d, keep
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -291,6 +321,9 @@ class NativeLib:
             ("tail_step_count", C.c_int64, [H]),
             ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
             ("ee_ik_solve", C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("raycast_create", C.c_int, [H, C.POINTER(RaycastScene), C.POINTER(CameraDesc), C.c_int32, _I32P]),
+            ("raycast_destroy", C.c_int, [H, C.c_int32]),
+            ("raycast_render", C.c_int, [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
         ):
             if hasattr(self.lib, self.prefix + name):
                 self._fn(name, restype, argtypes)
@@ -497,6 +530,28 @@ class NativeSim:
         if self.lib.ee_ik_solve is None:
             raise NativeError(f"{self.lib.path} has no ee_ik_solve (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.ee_ik_solve(self.h, target_pose_ptr, q0_ptr, q_out_ptr, iters_ptr, stream), "ee_ik_solve")
+
+    def raycast_create(self, scene_arrays: dict, cameras) -> int:
+        """a ray-cast scene and its cameras (a list of CameraDesc) -> id (HIP library only); raises NativeError with the
+        library's message where the scene is refused"""
+        if self.lib.raycast_create is None:
+            raise NativeError(f"{self.lib.path} has no raycast_create (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        scene, keep = make_raycast_scene(scene_arrays)
+        cams = (CameraDesc * max(len(cameras), 1))(*cameras)
+        rid = C.c_int32(-1)
+        self._check(self.lib.raycast_create(self.h, C.byref(scene), cams, len(cameras), C.byref(rid)), "raycast_create")
+        del keep
+        return rid.value
+
+    def raycast_destroy(self, rid: int):
+        if self.lib.raycast_destroy is None:
+            raise NativeError(f"{self.lib.path} has no raycast_destroy (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.raycast_destroy(self.h, int(rid)), "raycast_destroy")
+
+    def raycast_render(self, rid: int, camera: int, pos_seg_ptr, depth_ptr=None, stream=None):
+        if self.lib.raycast_render is None:
+            raise NativeError(f"{self.lib.path} has no raycast_render (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.raycast_render(self.h, int(rid), int(camera), pos_seg_ptr, depth_ptr, stream), "raycast_render")
 
     def task_pick_outputs(self, task: "PickTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
         self._check(self.lib.task_pick_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_pick_outputs")

@@ -87,6 +87,7 @@ class MssimSystem:
         self.num_envs = 0
         self._sim: Optional[native.NativeSim] = None
         self._queries: List = []
+        self._raycast_keep: Dict[int, tuple] = {}  # ray-cast scene id -> (tensors its cameras point to, the cameras' (width, height))
 
     # ------------------------------------------------------------------ lifecycle
     @property
@@ -409,6 +410,50 @@ class MssimSystem:
         """PullCubeTool evaluate / obs / reward in one launch; metrics [N][3] f32 = cube_to_workspace_dist, its progress
         term, dense reward / 5, required (include/mssim_hip_tasks.h; HIP library only)"""
         self._sim.task_pulltool_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), None if metrics is None else metrics.data_ptr(), self._stream())
+
+    # ------------------------------------------------------------------ ray-cast cameras (HIP only)
+    def raycast_create(self, scene_arrays: dict, cameras: Sequence[dict]) -> int:
+        """a ray-cast scene (`model.compile.raycast_scene`) with its cameras -> id for `raycast_render`
+        (include/mssim_hip_tasks.h `mssim_raycast_create`). A camera is a dict: width, height, fx, fy, cx, cy, near, far,
+        mount_row (-1: the env frame), pose (7 floats) or env_pose (a contiguous f32 [N, 7] tensor on the system's
+        device, read at every render; kept alive here)."""
+        descs, keep = [], []
+        for c in cameras:
+            d = native.CameraDesc(int(c["width"]), int(c["height"]), float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]),
+                                  float(c["near"]), float(c["far"]), int(c.get("mount_row", -1)))
+            pose = c.get("env_pose")
+            if pose is not None:
+                assert pose.dtype == torch.float32 and pose.is_contiguous() and tuple(pose.shape) == (self.num_envs, 7) and pose.device == self._rigid.device
+                keep.append(pose)
+                d.env_pose = pose.data_ptr()
+                d.pose = (native.C.c_float * 7)(0, 0, 0, 1, 0, 0, 0)
+            else:
+                d.pose = (native.C.c_float * 7)(*[float(x) for x in np.asarray(c["pose"], dtype=np.float64).reshape(7)])
+            descs.append(d)
+        rid = self._sim.raycast_create(scene_arrays, descs)
+        self._raycast_keep[rid] = (keep, [(int(c["width"]), int(c["height"])) for c in cameras])
+        return rid
+
+    def raycast_render(self, rid: int, camera: int, pos_seg: torch.Tensor, depth: Optional[torch.Tensor] = None):
+        """one launch on the current stream: `pos_seg` int16 [N, H, W, 4] (x, y, z in mm in the camera's OpenGL frame,
+        segmentation id), `depth` optional f32 [N, H, W] z-depth in metres; zeros where nothing is hit"""
+        sizes = self._raycast_sizes(rid)
+        if not 0 <= camera < len(sizes):
+            raise native.NativeError(f"raycast_render: scene {rid} has no camera {camera} (it has {len(sizes)})")
+        w, h = sizes[camera]
+        assert pos_seg.dtype == torch.int16 and pos_seg.is_contiguous() and tuple(pos_seg.shape) == (self.num_envs, h, w, 4)
+        assert depth is None or (depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (self.num_envs, h, w))
+        self._sim.raycast_render(rid, camera, pos_seg.data_ptr(), None if depth is None else depth.data_ptr(), self._stream())
+
+    def raycast_destroy(self, rid: int):
+        self._raycast_sizes(rid)
+        self._sim.raycast_destroy(rid)
+        del self._raycast_keep[rid]
+
+    def _raycast_sizes(self, rid: int):
+        if rid not in self._raycast_keep:
+            raise native.NativeError(f"no ray-cast scene with id {rid} on this system (raycast_create returns the ids; a destroyed one is gone)")
+        return self._raycast_keep[rid][1]
 
     def tail_step_count(self) -> int:
         """control steps so far that ran as one launch with the task epilogue at the kernel's tail (HIP library only)"""

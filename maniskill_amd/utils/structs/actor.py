@@ -33,6 +33,12 @@ class Actor(_RigidBase):
         self.merged = False
         self._fragment = None
         self._own_idx = None
+        self._per_scene_id = scene._new_per_scene_id()
+
+    @property
+    def per_scene_id(self) -> torch.Tensor:
+        """[N] int32: the id this actor has in segmentation images (the same in every env; 0 is the background)"""
+        return torch.full((self.scene.num_envs,), self._per_scene_id, dtype=torch.int32, device=self.device)
 
     @classmethod
     def merge(cls, actors: List["Actor"], name: str = None) -> "Actor":

@@ -17,6 +17,12 @@ class Link(_RigidBase):
         self.joint = joint
         self.merged = False
         self.disable_gravity_flag = False
+        self._per_scene_id = scene._new_per_scene_id()
+
+    @property
+    def per_scene_id(self) -> torch.Tensor:
+        """[N] int32: the id this link has in segmentation images (the same in every env; 0 is the background)"""
+        return torch.full((self.scene.num_envs,), self._per_scene_id, dtype=torch.int32, device=self.device)
 
     @property
     def index(self) -> torch.Tensor:
