@@ -277,31 +277,37 @@ int mssim_set_ee_ik_map(mssim_handle h, const mssim_ee_ik_map* map, float* targe
 int mssim_ee_ik_solve(mssim_handle h, const float* target_pose /* [N][7] */, const float* q0 /* [N][n_dof] or NULL = visible qpos */,
                       float* q_out /* [N][n_dof]; dofs off the path copied from q0 */, int32_t* iters_out /* optional [N] */, void* stream);
 
-/* ---- Ray-cast camera observations: depth, actor-level segmentation and camera-frame position --------------------
- * A scene is the geometry of one env as the ray caster sees it: analytic shapes and convex hulls (as face planes) on
- * rows of `rigid_body_data`, with the same optional per-env overrides as mssim_model_desc ([items][N], env fastest).
+/* ---- Ray-cast camera observations: depth, actor-level segmentation and position --------------------------------
+ * A scene is the geometry of one env as the ray caster sees it: analytic shapes, convex hulls (as face planes) and
+ * triangle meshes (the model's tri_soup and 16-wide tri_bvh) on rows of `rigid_body_data`, with the same optional per-env
+ * overrides as mssim_model_desc ([items][N], env fastest), per-env hulls and per-env segmentation ids included.
  * All arrays of the scene are HOST arrays, read once by mssim_raycast_create. Refused there (non-zero return code and
- * a last_error text, nothing is uploaded or launched): triangle-mesh shapes (shared or per env), a per-env CONVEX
- * type in a slot whose shared type is not CONVEX (per-env hulls), rows / plane ranges / slots out of range.
- * NOT detected: a slot whose shared type and per-env type are both CONVEX but whose hull differs from env to env -- the
- * scene carries one plane range per shape, every env renders it. Callers of this entry point must make sure themselves
- * that such a slot holds the same hull in every env (maniskill_amd/model/compile.py: raycast_scene refuses the model).
+ * a last_error text, nothing is uploaded or launched): a triangle-mesh shape in a scene without a triangle table, a
+ * per-env TRIMESH type in a slot whose shared type is not TRIMESH, a per-env CONVEX type in a slot whose shared type is
+ * not CONVEX, rows / plane ranges / triangle ranges / BVH references / slots out of range (per-env ranges in every
+ * env), a BVH whose child references form a cycle or that is deeper than MSSIM_RAYCAST_MESH_DEPTH levels.
  *
  * Conventions. The camera pose is in the SAPIEN convention (x forward, y left, z up), relative to the env frame
  * (mount_row < 0) or to the body of `mount_row`, whose pose the kernel reads from rigid_body_data itself. Pixel
  * (column u, row v) casts the ray o + t dir, dir = ((u + 0.5 - cx) / fx, (v + 0.5 - cy) / fy, 1) in the OpenCV camera
- * frame (x right, y down, z forward), not normalised: t is the z-depth. Every shape is convex; a shape's hit is its
- * ENTRY parameter, and counts when near <= t <= min(far, 32.767) -- a shape entered in front of `near`, or holding the
- * ray's start, gives no hit (back faces are culled), and a surface beyond the int16 millimetre range is "nothing". The
- * pixel takes the smallest hit of the env's shapes (the first shape in scene order on an exact tie).
+ * frame (x right, y down, z forward), not normalised: t is the z-depth. Every shape but a mesh is convex; such a shape's
+ * hit is its ENTRY parameter, and counts when near <= t <= min(far, 32.767) -- a shape entered in front of `near`, or
+ * holding the ray's start, gives no hit (back faces are culled), and a surface beyond the int16 millimetre range is
+ * "nothing". The pixel takes the smallest hit of the env's shapes (the first shape in scene order on an exact tie).
  * Shapes are intersected in their own frames: plane = the half space x <= 0, box = slabs, sphere, capsule / cylinder
- * about +x (side plus caps), convex = clip against the planes (a ray parallel to a plane and outside it misses). */
+ * about +x (side plus caps), convex = clip against the planes (a ray parallel to a plane and outside it misses).
+ * A triangle mesh is a SURFACE, not a solid: its hit is the smallest t in [near, min(far, 32.767)] over its triangles,
+ * each of them TWO-SIDED (a camera inside a closed mesh sees its walls; the winding of a triangle does not matter). The
+ * edge tests are inclusive: a ray through the shared edge or corner of two triangles hits at least one of them. A ray
+ * in a triangle's plane misses it. Ties between shapes go to the first in scene order, as above. */
 typedef struct mssim_raycast_scene {
   int32_t n_shape;
-  const int32_t* shape_type;     /* [n_shape] MSSIM_SHAPE_* (never MSSIM_SHAPE_TRIMESH)                                   */
+  const int32_t* shape_type;     /* [n_shape] MSSIM_SHAPE_*                                                                */
   const int32_t* shape_row;      /* [n_shape] rigid_body_data body row of the owner, -1 = fixed in the env frame          */
   const float* shape_frame;      /* [n_shape][7] p, q(wxyz): shape frame in the body (or env) frame                       */
-  const float* shape_param;      /* [n_shape][4] as mssim_model_desc.shape_param                                          */
+  const float* shape_param;      /* [n_shape][4] as mssim_model_desc.shape_param; TRIMESH: word 0 = first triangle in
+                                    tri_soup, word 1 = triangle count, word 2 = root node in tri_bvh (float-valued integers:
+                                    the model's shape_param words 0, 1 and its shape_hull word 0)                          */
   const float* shape_bound;      /* [n_shape][4] bounding sphere: centre in the BODY frame, radius; radius < 0 = unbounded */
   const int16_t* shape_seg;      /* [n_shape] segmentation id written where the shape is hit (0 is the background's)       */
   const int32_t* shape_planes;   /* [n_shape][2] CONVEX: first plane, plane count in `planes`; others ignored             */
@@ -310,9 +316,19 @@ typedef struct mssim_raycast_scene {
   int32_t n_env_shape;           /* per-env override slots                                                                 */
   const int32_t* shape_env_slot; /* [n_shape] slot or -1; may be NULL when n_env_shape == 0                                */
   const float* env_shape_frame;  /* [n_env_shape * 7][N]                                                                   */
-  const float* env_shape_param;  /* [n_env_shape * 4][N]: rows 0..2 parameters, row 3 = the env's MSSIM_SHAPE_* + 1
-                                    (MSSIM_SHAPE_NONE: the env has nothing in the slot), 0 = the shared type              */
+  const float* env_shape_param;  /* [n_env_shape * 4][N]: rows 0..2 parameters (TRIMESH: first triangle, triangle count,
+                                    root node of THIS env's mesh, as in mssim_model_desc), row 3 = the env's
+                                    MSSIM_SHAPE_* + 1 (MSSIM_SHAPE_NONE: the env has nothing in the slot), 0 = the shared type */
   const float* env_shape_bound;  /* [n_env_shape * 4][N]: centre in the BODY frame, radius                                 */
+  /* ---- members added for meshes and per-env hulls; 0 / NULL = absent ---- */
+  int32_t n_tri;
+  const float* tri_soup;         /* [n_tri][12] as mssim_model_desc.tri_soup: centroid, three corners relative to it      */
+  int32_t n_tri_node;
+  const float* tri_bvh;          /* [n_tri_node][112] as mssim_model_desc.tri_bvh                                          */
+  const int32_t* env_shape_planes; /* [n_env_shape * 2][N] first plane, plane count of the env's hull where the env's type
+                                    is CONVEX: a different hull per env. NULL: every env renders shape_planes[i]           */
+  const int16_t* env_shape_seg;  /* [n_env_shape][N] the id of the slot's shape in each env (the actor that owns the
+                                    geometry THERE). NULL: shape_seg[i] in every env                                       */
 } mssim_raycast_scene;
 
 typedef struct mssim_camera_desc {
@@ -326,6 +342,7 @@ typedef struct mssim_camera_desc {
 
 #define MSSIM_RAYCAST_MAX_MM 32767 /* the largest depth a pixel can carry, in millimetres */
 #define MSSIM_RAYCAST_CHUNK 64     /* shapes staged on chip at a time: a scene with more is walked in chunks of this many */
+#define MSSIM_RAYCAST_MESH_DEPTH 8 /* levels of tri_bvh nodes below (and with) a mesh's root that the kernel's traversal stack holds */
 
 /* Uploads the scene and the cameras; *id names them in the calls below. Allocates: not for the step loop. */
 int mssim_raycast_create(mssim_handle h, const mssim_raycast_scene* scene, const mssim_camera_desc* cameras, int32_t n_cameras, int32_t* id);

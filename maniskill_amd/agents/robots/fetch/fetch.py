@@ -24,6 +24,7 @@ from maniskill_amd.agents.controllers import (
     deepcopy_dict,
 )
 from maniskill_amd.agents.registration import register_agent
+from maniskill_amd.sensors.camera import CameraConfig
 from maniskill_amd.utils import common
 from maniskill_amd.utils.structs.pose import Pose
 
@@ -57,6 +58,18 @@ class Fetch(BaseAgent):
     arm_gains = (1e3, 1e2, 100)
     gripper_gains = (1e3, 1e2, 100)
     body_gains = (1e3, 1e2, 100)
+
+    @property
+    def _sensor_configs(self):
+        """the head camera and the one behind the gripper (fetch.py:52-74 of the reference), both 128 x 128 with a vertical
+        field of view of 2 rad"""
+        links = self.robot.links_map
+        return [
+            CameraConfig(uid="fetch_head", pose=Pose.create_from_pq(p=[0, 0, 0], q=[1, 0, 0, 0]), width=128, height=128, fov=2, near=0.01, far=100,
+                         mount=links["head_camera_link"]),
+            CameraConfig(uid="fetch_hand", pose=Pose.create_from_pq(p=[-0.1, 0, 0.1], q=[1, 0, 0, 0]), width=128, height=128, fov=2, near=0.01, far=100,
+                         mount=links["gripper_link"]),
+        ]
 
     @property
     def _controller_configs(self):

@@ -9,11 +9,21 @@
 // read from global memory at addresses that are the same in every lane. No atomics: one lane writes each pixel, with one
 // 8-byte store (and one 4-byte store for the float depth), so a render is deterministic.
 //
+// Triangle meshes (k_raycast<true>, chosen at create for a scene that holds one, or per-env plane ranges or ids, which
+// that instance alone reads while staging; k_raycast<false> is the kernel without any of them, register for register): a staged mesh passes the same bounding-sphere reject, then each lane walks the mesh's 16-wide BVH for its own ray,
+// depth first: at a node it tests the 16 child boxes (slabs, against [near, nearest hit so far]) into a 16-bit mask and
+// takes the children in index order; a leaf child is one triangle, intersected two-sided from its centroid and relative
+// corners (rc::triangle). A level's (node, children still to visit) waits in LDS while the lane is below it -- one 8-byte
+// word per lane and level, [level][lane] so that a wave's access is one contiguous 512 B --: no per-lane array, no
+// scratch. Node and triangle data are read from global memory; the rays of a wave are neighbours and mostly ask for the
+// same nodes, which the caches serve. mssim_raycast::validate bounds a mesh's depth by MSSIM_RAYCAST_MESH_DEPTH.
+//
 // The arithmetic (namespace rc) is plain C++ under RC_HD, so that a host build can run it too.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 
 #ifdef __HIPCC__
 #define RC_HD __host__ __device__ __forceinline__
@@ -186,10 +196,99 @@ RC_HD float enter(int type, const float* p, v3 o, v3 d, const float* __restrict_
   return tin <= tout ? tin : kInf;
 }
 
+
+// ---- triangle meshes (include/mssim_hip_tasks.h: a surface of two-sided triangles, inclusive edges) ----
+// Barycentric slack of the edge tests: a triangle counts as hit up to this far (in units of its own edges) outside it, so
+// that the float roundings of two triangles that share an edge cannot open a crack between them. 1e-5 of an edge -- 10
+// micrometres on a metre -- is a hundred float roundings and far less than a pixel anywhere.
+constexpr float kTriSlack = 1e-5f;
+
+// parameter of the ray (oc + t d, oc relative to the centroid) where it meets the triangle with corners a, b, c relative
+// to the centroid, from either side; +inf: no hit (outside, or the ray lies in the triangle's plane)
+RC_HD float triangle(v3 oc, v3 d, v3 a, v3 b, v3 c) {
+  const v3 e1 = b - a, e2 = c - a, s = oc - a;
+  const v3 p = mk(d.y * e2.z - d.z * e2.y, d.z * e2.x - d.x * e2.z, d.x * e2.y - d.y * e2.x);  // d x e2
+  const float det = dot(e1, p);
+  if (det == 0.f) return kInf;
+  const float inv = 1.f / det;
+  const float u = dot(s, p) * inv;
+  const v3 q = mk(s.y * e1.z - s.z * e1.y, s.z * e1.x - s.x * e1.z, s.x * e1.y - s.y * e1.x);  // s x e1
+  const float v = dot(d, q) * inv;
+  if (!(u >= -kTriSlack && v >= -kTriSlack && u + v <= 1.f + kTriSlack)) return kInf;
+  return dot(e2, q) * inv;
+}
+
+// which of a node's 16 child boxes the ray meets within [lo, hi]: bit c = child c. The boxes bound the corners exactly
+// (model/mesh.py builds them from the float corners), the slab arithmetic rounds: a relative slack on the interval keeps
+// a flat box -- an axis-aligned triangle's -- from slipping between two roundings. `inv` = 1 / d per axis (+-inf where
+// d is 0: a NaN from 0 x inf is dropped by fminf / fmaxf, which reads as "inside the slab", the safe side).
+RC_HD unsigned node_mask(const float* __restrict__ node, v3 o, v3 inv, float lo, float hi) {
+  unsigned mask = 0u;
+  for (int c = 0; c < 16; c++) {
+    const float* b = node + 6 * c;
+    if (!(b[0] <= b[3])) continue;  // no child
+    const float x1 = (b[0] - o.x) * inv.x, x2 = (b[3] - o.x) * inv.x;
+    const float y1 = (b[1] - o.y) * inv.y, y2 = (b[4] - o.y) * inv.y;
+    const float z1 = (b[2] - o.z) * inv.z, z2 = (b[5] - o.z) * inv.z;
+    const float tin = fmaxf(fmaxf(fminf(x1, x2), fminf(y1, y2)), fmaxf(fminf(z1, z2), lo));
+    const float tout = fminf(fminf(fmaxf(x1, x2), fmaxf(y1, y2)), fminf(fmaxf(z1, z2), hi));
+    if (tin <= tout + 4e-6f * (fabsf(tin) + fabsf(tout)) + 1e-7f) mask |= 1u << c;
+  }
+  return mask;
+}
+
+struct MeshLevel { int node; unsigned mask; };  // a level of the walk: the node and its children still to visit
+
+// smallest t in [near, tmax] below `best` over the triangles of the mesh under `root` (shape frame: o, d); `best` where
+// there is none. `stack` holds MSSIM_RAYCAST_MESH_DEPTH levels, `stride` elements apart.
+RC_HD float mesh_hit(const float* __restrict__ bvh, const float* __restrict__ soup, int root, v3 o, v3 d, float near, float tmax, float best,
+                     MeshLevel* stack, int stride) {
+  const v3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
+  best = fminf(best, tmax);
+  bool found = false;
+  int sp = 0, node = root;
+  unsigned mask = node_mask(bvh + (size_t)node * 112, o, inv, near, best);
+  for (;;) {
+    if (mask == 0u) {
+      if (sp == 0) break;
+      sp--;
+      node = stack[sp * stride].node; mask = stack[sp * stride].mask;
+      continue;
+    }
+    const int c = __builtin_ctz(mask);
+    mask &= mask - 1u;
+    const float* nd = bvh + (size_t)node * 112;
+    int ref;
+#ifdef __HIP_DEVICE_COMPILE__
+    ref = __float_as_int(nd[96 + c]);
+#else
+    memcpy(&ref, nd + 96 + c, 4);
+#endif
+    if (ref < 0) {
+      const float* q = soup + (size_t)(~ref) * 12;
+      const float t = triangle(mk(o.x - q[0], o.y - q[1], o.z - q[2]), d, mk(q[3], q[4], q[5]), mk(q[6], q[7], q[8]), mk(q[9], q[10], q[11]));
+      if (t >= near && t <= tmax && (found ? t < best : t <= best)) { best = t; found = true; }
+      continue;
+    }
+    if (mask != 0u) {
+      if (sp == MSSIM_RAYCAST_MESH_DEPTH) continue;  // (never: validate bounds the depth; a deeper branch is left out, not overrun)
+      stack[sp * stride].node = node; stack[sp * stride].mask = mask;
+      sp++;
+    }
+    node = ref;
+    mask = node_mask(bvh + (size_t)node * 112, o, inv, near, best);
+  }
+  return found ? best : kInf;
+}
+
 struct Hit { float t; int seg; };
 
-// one pixel's ray (x_cv, y_cv, 1) against staged shapes [0, n): improves `hit` (strictly smaller t only)
-RC_HD void trace(const Staged* __restrict__ sh, int n, const float* __restrict__ planes, float xcv, float ycv, float near, float tmax, bool live, Hit* hit) {
+// one pixel's ray (x_cv, y_cv, 1) against staged shapes [0, n): improves `hit` (strictly smaller t only). MESH: a staged
+// TRIMESH shape (pl0 = its root node) is walked through `bvh` / `soup` with the lane's `stack`; without it such a shape is
+// never staged (validate turns a mesh down for a scene without triangle tables, and those choose MESH).
+template <bool MESH>
+RC_HD void trace(const Staged* __restrict__ sh, int n, const float* __restrict__ planes, float xcv, float ycv, float near, float tmax, bool live, Hit* hit,
+                 const float* __restrict__ bvh = nullptr, const float* __restrict__ soup = nullptr, MeshLevel* stack = nullptr, int stride = 0) {
   const float dd = xcv * xcv + ycv * ycv + 1.f;
   for (int i = 0; i < n; i++) {
     const Staged& s = sh[i];
@@ -211,7 +310,9 @@ RC_HD void trace(const Staged* __restrict__ sh, int n, const float* __restrict__
     if (need) {
       const v3 o = mk(s.ox, s.oy, s.oz);
       const v3 d = mk(s.r0[0] * xcv + s.r0[1] * ycv + s.r0[2], s.r1[0] * xcv + s.r1[1] * ycv + s.r1[2], s.r2[0] * xcv + s.r2[1] * ycv + s.r2[2]);
-      const float t = enter(s.type, s.p, o, d, planes, s.pl0, s.pln);
+      float t;
+      if (MESH && s.type == MSSIM_SHAPE_TRIMESH) t = mesh_hit(bvh, soup, s.pl0, o, d, near, tmax, hit->t, stack, stride);
+      else t = enter(s.type, s.p, o, d, planes, s.pl0, s.pln);
       if (t >= near && t <= tmax && t < hit->t) { hit->t = t; hit->seg = s.seg; }
     }
   }
@@ -232,6 +333,8 @@ struct RcTables {
   const int* type; const int* row; const float* frame; const float* param; const float* bound; const int* seg; const int* planes2;
   const float* plane;
   const int* env_slot; const float* env_frame; const float* env_param; const float* env_bound;  // env_slot null: no overrides
+  const int* env_planes2; const int* env_seg;  // [slots * 2][N], [slots][N]; null: the shared plane range / id in every env
+  const float* tri_soup; const float* tri_bvh;  // null without meshes
 };
 
 struct RcCamera {
@@ -243,14 +346,19 @@ struct RcObject {
   std::vector<RcCamera> cams;
   std::vector<void*> allocs;
   bool needs_rows = false;  // some shape or camera rides on a body row
+  bool mesh = false;        // the scene holds a triangle mesh, per-env plane ranges or per-env ids: k_raycast<true>
   ~RcObject() { for (void* p : allocs) (void)hipFree(p); }
 };
 
 constexpr int RC_TILE = 16;
 
+// MESH: the scene holds triangle meshes, per-env hulls or per-env ids (see the head of this file); false is the kernel as
+// it is without them
+template <bool MESH>
 __global__ __launch_bounds__(256) void k_raycast(RcTables T, RcCamera C, const float* __restrict__ rigid, int N, int tiles_x, int tiles,
                                                  short* __restrict__ pos_seg, float* __restrict__ depth) {
   __shared__ __attribute__((aligned(16))) rc::Staged sh[MSSIM_RAYCAST_CHUNK];
+  __shared__ __attribute__((aligned(8))) rc::MeshLevel levels[MESH ? MSSIM_RAYCAST_MESH_DEPTH * 256 : 1];  // [level][lane]
   const int env = blockIdx.x / tiles, tile = blockIdx.x - env * tiles;
   if (env >= N) return;  // (never: the grid is N * tiles)
   const int tx = tile % tiles_x, ty = tile / tiles_x;
@@ -281,7 +389,7 @@ __global__ __launch_bounds__(256) void k_raycast(RcTables T, RcCamera C, const f
         const float* eb = T.env_bound + (size_t)slot * 4 * N + env;
         const int t1 = (int)ep[3 * (size_t)N];
         if (t1 > 0) type = t1 - 1;
-        if (type != MSSIM_SHAPE_CONVEX) { param[0] = ep[0]; param[1] = ep[(size_t)N]; param[2] = ep[2 * (size_t)N]; }
+        if (type != MSSIM_SHAPE_CONVEX && !(MESH && type == MSSIM_SHAPE_TRIMESH && t1 == 0)) { param[0] = ep[0]; param[1] = ep[(size_t)N]; param[2] = ep[2 * (size_t)N]; }
         bc = rc::p3{eb[0], eb[(size_t)N], eb[2 * (size_t)N]};
         br = eb[3 * (size_t)N];
       }
@@ -291,10 +399,16 @@ __global__ __launch_bounds__(256) void k_raycast(RcTables T, RcCamera C, const f
         frame = rc::compose(body, frame);
         bc = body.p + rc::qrot(body.q, bc);
       }
-      sh[threadIdx.x] = rc::stage(cam, frame, bc, br, type, param, T.seg[i], T.planes2[2 * i], T.planes2[2 * i + 1]);
+      int seg = T.seg[i], pl0 = T.planes2[2 * i], pln = T.planes2[2 * i + 1];
+      if (MESH && slot >= 0) {  // the env's own hull and id (tables that only this variant reads: see RcObject::mesh)
+        if (T.env_planes2 && type == MSSIM_SHAPE_CONVEX) { pl0 = T.env_planes2[(size_t)slot * 2 * N + env]; pln = T.env_planes2[((size_t)slot * 2 + 1) * N + env]; }
+        if (T.env_seg) seg = T.env_seg[(size_t)slot * N + env];
+      }
+      if (MESH && type == MSSIM_SHAPE_TRIMESH) { pl0 = (int)param[2]; pln = (int)param[1]; }  // root node, triangle count
+      sh[threadIdx.x] = rc::stage(cam, frame, bc, br, type, param, seg, pl0, pln);
     }
     __syncthreads();
-    rc::trace(sh, n, T.plane, xcv, ycv, C.near, C.tmax, live, &hit);
+    rc::trace<MESH>(sh, n, T.plane, xcv, ycv, C.near, C.tmax, live, &hit, T.tri_bvh, T.tri_soup, levels + (MESH ? threadIdx.x : 0), 256);
   }
   if (!live) return;
   const bool any = hit.t < rc::kInf;
@@ -332,6 +446,7 @@ int mssim_raycast_create(mssim_handle h, const mssim_raycast_scene* s, const mss
   for (size_t i = 0; i < n; i++) {
     seg[i] = (int)(uint16_t)s->shape_seg[i];
     o->needs_rows = o->needs_rows || s->shape_row[i] >= 0;
+    o->mesh = o->mesh || s->shape_type[i] == MSSIM_SHAPE_TRIMESH;  // (a per-env mesh lives in a slot whose shared type is one)
   }
   RcTables& T = o->T;
   T.n_shape = s->n_shape;
@@ -349,6 +464,18 @@ int mssim_raycast_create(mssim_handle h, const mssim_raycast_scene* s, const mss
     if (int rc = rc_upload(h, o.get(), s->env_shape_frame, 7 * ne, &T.env_frame)) return rc;
     if (int rc = rc_upload(h, o.get(), s->env_shape_param, 4 * ne, &T.env_param)) return rc;
     if (int rc = rc_upload(h, o.get(), s->env_shape_bound, 4 * ne, &T.env_bound)) return rc;
+    if (s->env_shape_planes)
+      if (int rc = rc_upload(h, o.get(), s->env_shape_planes, 2 * ne, &T.env_planes2)) return rc;
+    if (s->env_shape_seg) {
+      std::vector<int> eseg(ne);
+      for (size_t k = 0; k < ne; k++) eseg[k] = (int)(uint16_t)s->env_shape_seg[k];
+      if (int rc = rc_upload(h, o.get(), eseg.data(), ne, &T.env_seg)) return rc;
+    }
+  }
+  o->mesh = o->mesh || T.env_planes2 || T.env_seg;  // (k_raycast<false> stays the kernel it was: it reads neither table)
+  if (s->n_tri > 0 && s->n_tri_node > 0 && o->mesh) {
+    if (int rc = rc_upload(h, o.get(), s->tri_soup, 12 * (size_t)s->n_tri, &T.tri_soup)) return rc;
+    if (int rc = rc_upload(h, o.get(), s->tri_bvh, 112 * (size_t)s->n_tri_node, &T.tri_bvh)) return rc;
   }
   for (int c = 0; c < n_cameras; c++) {
     const mssim_camera_desc& k = cameras[c];
@@ -381,8 +508,9 @@ int mssim_raycast_render(mssim_handle h, int32_t id, int32_t camera, int16_t* po
   if (o.needs_rows && !h->buf.rigid_body_data) { h->err = "raycast_render: no rigid_body_data bound"; return 1; }
   const RcCamera& C = o.cams[camera];
   const int tiles_x = (C.width + RC_TILE - 1) / RC_TILE, tiles = tiles_x * ((C.height + RC_TILE - 1) / RC_TILE);
-  hipLaunchKernelGGL(k_raycast, dim3((unsigned)(tiles * h->N)), dim3(256), 0, (hipStream_t)stream, o.T, C, h->buf.rigid_body_data, h->N, tiles_x, tiles,
-                     (short*)pos_seg, depth_f32);
+  const auto kernel = o.mesh ? k_raycast<true> : k_raycast<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles * h->N)), dim3(256), 0, (hipStream_t)stream, o.T, C, h->buf.rigid_body_data,
+                     h->N, tiles_x, tiles, (short*)pos_seg, depth_f32);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -246,15 +246,24 @@ class BaseEnv(gym.Env):
             self._sensors[uid] = Camera(config, self.scene, self.agent.robot if uid in self._agent_sensor_configs else None, rig=rig)
         self.scene.sensors = self._sensors
 
-    def _segmentation_ids_by_owner(self) -> Dict[str, int]:
-        """the compiled model's shape owner names (an actor's body row name, a link's name) -> segmentation id"""
-        return {getattr(o, "_row_name", None) or o.name: i for i, o in self.segmentation_id_map.items()}
+    def _segmentation_ids_by_owner(self) -> Dict[str, Any]:
+        """the compiled model's shape owner names (an actor's body row name, a link's name) -> segmentation id; for a body
+        row shared by the actors of different sub-scenes, one id per env [N]: the actor's that is in that env (0: nobody's)"""
+        ids: Dict[str, Any] = {}
+        for i, o in self.segmentation_id_map.items():
+            row_name = getattr(o, "_row_name", None)
+            if row_name is None:
+                ids[o.name] = i
+                continue
+            per_env = ids.setdefault(row_name, np.zeros(self.num_envs, dtype=np.int16))
+            per_env[common.to_numpy(o._own_idx)] = i
+        return ids
 
     @cached_property
     def segmentation_id_map(self) -> Dict[int, Union[Actor, Any]]:
         """segmentation id (`per_scene_id`; 0 is the background) -> the Actor or Link that carries it"""
         structs = list(self.scene.actors.values()) + [link for art in self.scene.articulations.values() for link in art.links]
-        # (actors that share a body row across sub-scenes share an id: the first one built stands for the row)
+        # (actors that share a body row across sub-scenes keep their own ids: the row's shapes carry an id per env)
         by_id: Dict[int, Any] = {}
         for struct in sorted(structs, key=lambda o: o._per_scene_id):
             by_id.setdefault(struct._per_scene_id, struct)

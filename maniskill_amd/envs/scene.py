@@ -210,8 +210,9 @@ class ManiSkillScene:
             shared = Actor.merge(group, name=f"shared-dynamic-body-{k}")
             self.actors.pop(shared.name)
             for f, name, envs, init, masses in members:
+                own_id = f._per_scene_id  # (each keeps the segmentation id it was built with: the row's geometry is this actor's in its envs)
                 f.__dict__.update(shared.__dict__)
-                f.name, f._row_name = name, shared.name
+                f.name, f._row_name, f._per_scene_id = name, shared.name, own_id
                 f._own_idx = torch.tensor(sorted(envs), dtype=torch.long, device=self.device)
                 f.initial_pose = Pose.create(init.raw_pose[:1].expand(len(envs), 7).clone())
                 f._mass_per_env = torch.tensor(masses, dtype=torch.float32)

@@ -8,9 +8,12 @@ The reference's default builder is ReplicaCAD; its assets are not available here
 """
 from typing import Union
 
+import numpy as np
 import torch
 
 from maniskill_amd.envs.sapien_env import BaseEnv
+from maniskill_amd.sensors.camera import CameraConfig
+from maniskill_amd.utils import sapien_utils
 from maniskill_amd.utils.registration import register_env
 from maniskill_amd.utils.scene_builder import REGISTERED_SCENE_BUILDERS, SceneBuilder
 from maniskill_amd.utils.scene_builder import synthetic_rooms  # noqa: F401  (registers "SyntheticRooms")
@@ -47,6 +50,14 @@ class SceneManipulationEnv(BaseEnv):
             assert "build_config_idxs" not in options, "options dict cannot contain build_config_idxs without reconfigure=True"
             self.init_config_idxs = _as_list(options.get("init_config_idxs", self.init_config_idxs))
         return super().reset(seed=seed, options=options)
+
+    @property
+    def _default_sensor_configs(self):
+        """the Fetch looks through its own cameras (fetch_head, fetch_hand); a fixed-base arm gets one camera on its workspace
+        (base_env.py:153-159 of the reference)"""
+        if self.robot_uids == "fetch":
+            return []
+        return [CameraConfig("base_camera", sapien_utils.look_at([0.3, 0, 0.6], [-0.1, 0, 0.1]), 128, 128, np.pi / 2, 0.01, 100)]
 
     def _load_lighting(self, options: dict):
         if not self.scene_builder.builds_lighting:

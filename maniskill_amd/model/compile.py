@@ -656,43 +656,74 @@ class SceneModelBuilder:
         )
 
 
-def raycast_scene(model: CompiledModel, seg_ids: Dict[str, int]) -> Dict[str, np.ndarray]:
+def raycast_scene(model: CompiledModel, seg_ids: Dict[str, object], meshes: bool = False) -> Dict[str, np.ndarray]:
     """The ray caster's view of a compiled model (`mssim_raycast_scene`, include/mssim_hip_tasks.h): every collision
     shape with its body row, hull face planes instead of hull vertices, bounding spheres about a centre in the BODY
-    frame, and a segmentation id per shape from `seg_ids` (owner name -> id >= 1; shapes of owners it does not name get
-    0, the background's). Per-env overrides are passed on as the model holds them. Raises ValueError for what the ray
-    caster leaves out: triangle meshes and hulls that differ from env to env."""
+    frame, and a segmentation id per shape from `seg_ids` (owner name -> id >= 1, or -> one id per env [N] where the
+    actors of different sub-scenes share the owner's body row; shapes of owners it does not name get 0, the background's).
+    Per-env overrides are passed on as the model holds them; a slot whose hull differs from env to env gets a plane range
+    per env (`env_shape_planes`; face planes are computed once per distinct hull), a slot whose owner differs from env to
+    env an id per env (`env_shape_seg`). Triangle meshes need `meshes=True`: the scene then carries the model's `tri_soup`
+    and `tri_bvh`, and a mesh shape names its triangles and root node in `shape_param`. Without it a model with a mesh
+    raises ValueError, as does a hull in a slot whose shared type is not a hull (mssim_raycast_create refuses it)."""
     A, N = model.arrays, int(model.scalars["num_envs"])
     ns = int(model.scalars["n_shape"])
     types, slots = A["shape_type"], A["shape_env_slot"]
     n_es = int(model.scalars["n_env_shape"])
     env_param = A["env_shape_param"].reshape(n_es, 4, -1) if n_es else np.zeros((0, 4, N), dtype=np.float32)
     bound = np.zeros((ns, 4), dtype=np.float32)
+    param = np.array(A["shape_param"], dtype=np.float32).reshape(ns, 4)
     planes, ranges, seg = [], np.zeros((ns, 2), dtype=np.int32), np.zeros(ns, dtype=np.int16)
+    env_ranges, env_seg = np.zeros((n_es, 2, N), dtype=np.int32), np.zeros((n_es, N), dtype=np.int16)
+    per_env_hulls = per_env_ids = has_mesh = False
+    hull_ranges = {}  # (first vertex, count) -> (first plane, count)
+
+    def planes_of(first, count):
+        if (first, count) not in hull_ranges:
+            p = mesh.hull_face_planes(np.asarray(A["hull_verts"][first : first + count], dtype=np.float64))
+            hull_ranges[(first, count)] = (len(planes), len(p))
+            planes.extend(p.tolist())
+        return hull_ranges[(first, count)]
+
     for i in range(ns):
         owner = model.shape_owner[i]
         env_types = {int(types[i])} if slots[i] < 0 else {int(t) - 1 if t > 0 else int(types[i]) for t in np.unique(env_param[slots[i], 3])}
         if SHAPE_TRIMESH in env_types:
-            raise ValueError(f"{owner}: triangle-mesh shapes are out of scope of the ray caster (state observations only for this scene)")
+            if not meshes:
+                raise ValueError(f"{owner}: triangle-mesh shapes are left out of this ray-cast scene (ask for them with meshes=True)")
+            has_mesh = True
+        if types[i] == SHAPE_TRIMESH:
+            param[i, 2] = float(A["shape_hull"][i, 0])  # root node (words 0, 1: first triangle, count -- as the per-env rows)
         if SHAPE_CONVEX in env_types:
+            if types[i] != SHAPE_CONVEX:
+                raise ValueError(f"{owner}: a hull in a slot whose shared type is not a hull is out of scope of the ray caster")
             first, count = (int(x) for x in A["shape_hull"][i])
+            ranges[i] = planes_of(first, count)
             if slots[i] >= 0:
                 e = env_param[slots[i]]
-                own = e[3] == SHAPE_CONVEX + 1
-                if types[i] != SHAPE_CONVEX or np.any(e[0][own] != first) or np.any(e[1][own] != count):
-                    raise ValueError(f"{owner}: hulls that differ from env to env are out of scope of the ray caster")
-            p = mesh.hull_face_planes(np.asarray(A["hull_verts"][first : first + count], dtype=np.float64))
-            ranges[i] = (len(planes), len(p))
-            planes.extend(p.tolist())
+                for env in np.nonzero(e[3] == SHAPE_CONVEX + 1)[0]:
+                    env_ranges[slots[i], :, env] = planes_of(int(e[0, env]), int(e[1, env]))
+                    per_env_hulls = per_env_hulls or tuple(env_ranges[slots[i], :, env]) != tuple(ranges[i])
+                env_ranges[slots[i]][:, e[3] == 0] = np.asarray(ranges[i])[:, None]
         c, r = A["shape_bound"][i, :3].astype(np.float64), float(A["shape_bound"][i, 3])
         bound[i, :3] = geom.transform_point(A["shape_frame"][i].astype(np.float64), c) if r >= 0 else 0.0
         bound[i, 3] = r
-        seg[i] = int(seg_ids.get(owner, 0))
-    return dict(
+        ids = seg_ids.get(owner, 0)
+        if np.ndim(ids) == 0:
+            seg[i] = int(ids)
+            if slots[i] >= 0:
+                env_seg[slots[i]] = int(ids)
+        else:  # one id per env: the actor that owns this row's geometry there (0 where nobody does)
+            ids = np.asarray(ids, dtype=np.int16).reshape(N)
+            assert slots[i] >= 0, f"{owner}: per-env ids need a per-env shape slot"
+            env_seg[slots[i]] = ids
+            seg[i] = int(ids[np.argmax(ids != 0)])
+            per_env_ids = per_env_ids or bool((ids != seg[i]).any())
+    out = dict(
         shape_type=np.ascontiguousarray(types, dtype=np.int32),
         shape_row=np.ascontiguousarray(A["shape_row"], dtype=np.int32),
         shape_frame=np.ascontiguousarray(A["shape_frame"], dtype=np.float32),
-        shape_param=np.ascontiguousarray(A["shape_param"], dtype=np.float32),
+        shape_param=param,
         shape_bound=bound,
         shape_seg=seg,
         shape_planes=ranges,
@@ -703,3 +734,10 @@ def raycast_scene(model: CompiledModel, seg_ids: Dict[str, int]) -> Dict[str, np
         env_shape_param=A["env_shape_param"],
         env_shape_bound=A["env_shape_bound"],
     )
+    if has_mesh:
+        out["tri_soup"], out["tri_bvh"] = A["tri_soup"], A["tri_bvh"]
+    if per_env_hulls:
+        out["env_shape_planes"] = np.ascontiguousarray(env_ranges.reshape(2 * n_es, N))
+    if per_env_ids:
+        out["env_shape_seg"] = env_seg
+    return out

@@ -230,7 +230,13 @@ class RaycastScene(C.Structure):
     _fields_ = [("n_shape", C.c_int32), ("shape_type", _I32P), ("shape_row", _I32P), ("shape_frame", _F32P), ("shape_param", _F32P),
                 ("shape_bound", _F32P), ("shape_seg", _I16P), ("shape_planes", _I32P), ("n_plane", C.c_int32), ("planes", _F32P),
                 ("n_env_shape", C.c_int32), ("shape_env_slot", _I32P), ("env_shape_frame", _F32P), ("env_shape_param", _F32P),
-                ("env_shape_bound", _F32P)]
+                ("env_shape_bound", _F32P),
+                ("n_tri", C.c_int32), ("tri_soup", _F32P), ("n_tri_node", C.c_int32), ("tri_bvh", _F32P), ("env_shape_planes", _I32P),
+                ("env_shape_seg", _I16P)]
+
+
+# members of the scene a caller may leave out (NULL / 0: no meshes, the shared plane range and id in every env)
+_RAYCAST_OPTIONAL = ("tri_soup", "tri_bvh", "env_shape_planes", "env_shape_seg")
 
 
 class CameraDesc(C.Structure):
@@ -244,7 +250,11 @@ def make_raycast_scene(arrays: dict):
     same keys); keepalive must outlive the create call."""
     d, keep = RaycastScene(), []
     d.n_shape, d.n_plane, d.n_env_shape = len(arrays["shape_type"]), len(arrays["planes"]), int(arrays.get("n_env_shape", 0))
+    d.n_tri = len(arrays["tri_soup"]) if arrays.get("tri_soup") is not None else 0
+    d.n_tri_node = len(arrays["tri_bvh"]) if arrays.get("tri_bvh") is not None else 0
     for name, ctype in RaycastScene._fields_:
+        if name in _RAYCAST_OPTIONAL and arrays.get(name) is None:
+            continue
         if ctype in (_I32P, _F32P, _I16P):
             a = np.ascontiguousarray(arrays[name], dtype={_I32P: np.int32, _F32P: np.float32, _I16P: np.int16}[ctype])
             keep.append(a)

@@ -85,8 +85,9 @@ _GL_TO_CV = np.diag([1.0, -1.0, -1.0, 1.0])
 
 
 class RaycastRig:
-    """The cameras of one env object on one native ray-cast scene. The scene (hull face planes, segmentation ids) is
-    built and uploaded at the first capture, so that an env that never looks through its cameras pays nothing."""
+    """The cameras of one env object on one native ray-cast scene. The scene (hull face planes, triangle meshes with
+    their BVH, segmentation ids) is built and uploaded at the first capture, so that an env that never looks through its
+    cameras pays nothing."""
 
     def __init__(self, scene, seg_ids: Dict[str, int]):
         self.scene, self.seg_ids = scene, seg_ids
@@ -103,7 +104,7 @@ class RaycastRig:
         if self._id is None:
             from maniskill_amd.model.compile import raycast_scene
 
-            self._id = px.raycast_create(raycast_scene(self.scene.model, self.seg_ids), [c._desc() for c in self.cameras])
+            self._id = px.raycast_create(raycast_scene(self.scene.model, self.seg_ids, meshes=True), [c._desc() for c in self.cameras])
         if camera._pos_seg is None:
             camera._pos_seg = torch.zeros((self.scene.num_envs, camera.height, camera.width, 4), dtype=torch.int16, device=self.scene.device)
         px.raycast_render(self._id, camera._index, camera._pos_seg)

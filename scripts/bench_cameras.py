@@ -1,7 +1,9 @@
 """env-steps/s with the ray-cast camera observations beside the state observations, and the ray-cast launch's mean time by
 device events: `--env-id` (PickCube-v1) at `--num-envs` (1024) envs with `--obs-mode` (depth+segmentation), the cameras at
 `--size` (128) pixels square, random actions, `--runs` (3) runs of `--steps` (200) steps after `--warmup` (20) steps without a
-reset in between, in one process; then the same loop with obs_mode="state". One JSON line per mode, then both as RESULT."""
+reset in between, in one process; then the same loop with obs_mode="state". One JSON line per mode, then both as RESULT.
+`--camera` keeps one of the env's cameras (e.g. fetch_head of SceneManipulation-v1's Fetch) and drops the others before the
+first step; `--robot-uids` picks the robot of an env that offers several."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,12 +18,19 @@ ap.add_argument("--size", type=int, default=128)
 ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--warmup", type=int, default=20)
 ap.add_argument("--runs", type=int, default=3)
+ap.add_argument("--camera", default=None, help="render this camera only (default: every camera the env declares)")
+ap.add_argument("--robot-uids", default=None, help="the env's robot (default: the env's own default)")
 args = ap.parse_args()
 N, STEPS, WARMUP, RUNS = args.num_envs, args.steps, args.warmup, args.runs
 
 out = {}
 for mode in (args.obs_mode, "state"):
-    env = gym.make(args.env_id, num_envs=N, obs_mode=mode, sensor_configs=dict(width=args.size, height=args.size)).unwrapped
+    robot = dict(robot_uids=args.robot_uids) if args.robot_uids is not None else {}
+    env = gym.make(args.env_id, num_envs=N, obs_mode=mode, sensor_configs=dict(width=args.size, height=args.size), **robot).unwrapped
+    if args.camera is not None:
+        for uid in [u for u in env._sensors if u != args.camera]:
+            del env._sensors[uid]
+        assert list(env._sensors) == [args.camera], f"{args.env_id} has no camera {args.camera!r}"
     env.reset(seed=0)
     g = torch.Generator(device=env.device).manual_seed(1)
     actions = [2 * torch.rand(N, *env.single_action_space.shape, device=env.device, generator=g) - 1 for _ in range(max(STEPS, WARMUP))]
