@@ -1,15 +1,24 @@
-// mssim_collide.h -- per-lane narrowphase for gfx950 (one (env, shape pair) per lane).
+// mssim_collide.h -- manifold routines of the narrowphase for gfx950, written for one shape pair per lane.
 //
 // Replaces the contact generation hidden in `px.step()` (mani_skill/envs/scene.py:374-375; shape
 // types mani_skill/utils/building/actor_builder.py:73-155; contact_offset / rest_offset
 // mani_skill/utils/structs/types.py:40-41).
 //
-// Launch shape (see k_narrow): blockIdx.y = pair, so all 64 lanes of a wave work on the SAME
-// shape pair -- shape types, sizes and hull vertex addresses are wave-uniform (SGPR / scalar
-// loads), only poses differ per lane. Variable-length per-lane lists (clip polygons) live in
-// LDS as [slot][lane] so a lane-varying slot index is conflict-free (bank = lane % 32).
+// Callers: the narrowphase of the fused control-step kernel k_solve16 (mssim_solve16.h), and the test hook k_test_collide
+// (mssim_test_collide.h). In k_solve16 a 16-lane group is one env (or one row of it) and the pairs that survive the cull of
+// a wave's envs are worked on in three stages:
+//   stage A  one (env, pair) per lane: collide_plane for (plane, primitive), and collide_box_box<16> when the wave has more
+//            than S16_MAX_BBC box-box pairs that fit one round. The clip polygons of a lane live in the LDS area of its
+//            16-lane group as [slot][16 lanes], so a lane-varying slot index is conflict-free.
+//   stage B  one pair per 16-lane group: collide_mpr_t with the cooperative hull scan SupCoop16 (mssim_solve16.h), behind
+//            the persistent-manifold cache
+//   stage C  one pair per 16-lane group: collide_box_box_coop and, for (plane, hull), collide_plane_hull_coop
+//            (both in mssim_solve16.h; bb_setup below is shared by the two box-box routines)
+// collide_mpr (SupDirect: support() per lane, hull scans included) is the per-lane form of the same MPR; k_solve16 does not
+// call it today (its SupCoop16 falls back to support() for every shape but a hull), the test hook does. Shape types differ
+// from lane to lane.
 //
-//   plane  vs X      analytic, 4 deepest vertices
+//   plane  vs X      analytic, 4 deepest vertices (a hull: collide_plane_hull_coop, 4 by extent when it lies on a face)
 //   box    vs box    SAT over 15 axes + reference-face clipping, <= 4 points
 //   convex vs convex Minkowski Portal Refinement, shape A inflated by the contact offset, 1 point
 //
@@ -136,23 +145,7 @@ MS_DEV void collide_plane(const shape_t& pl, const shape_t& b, float offset, man
     f3 ax = mcol(b.rot, 0) * b.p1;
     add(b.c - ax, b.p0);
     add(b.c + ax, b.p0);
-  } else if (b.type == SH_CONVEX) {
-    // (batches of 8 vertices as six aligned 16-byte loads, as in support(): a vertex at a time is three dependent trips to
-    // L2 for the one lane that does this pair -- the Fetch's base hulls over the ground plane cost 10 % of its control step)
-    const int nv = b.nverts < 64 ? b.nverts : 64;
-    for (int i0 = 0; i0 < nv; i0 += 8) {
-      const float4* __restrict__ q = reinterpret_cast<const float4*>(b.verts + 3 * i0);
-      float f[24];
-#pragma unroll
-      for (int k = 0; k < 6; k++) {
-        const float4 t = q[k];
-        f[4 * k] = t.x; f[4 * k + 1] = t.y; f[4 * k + 2] = t.z; f[4 * k + 3] = t.w;
-      }
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        if (i0 + k < nv) add(b.c + mmulv(b.rot, f3{f[3 * k], f[3 * k + 1], f[3 * k + 2]}), 0.f);
-    }
-  } else {
+  } else {  // (a cylinder. A hull never comes here: collide_plane_hull_coop in mssim_solve16.h, which knows the extent rule)
     add(support(b, -np), 0.f);
   }
 }
@@ -161,8 +154,8 @@ MS_DEV void collide_plane(const shape_t& pl, const shape_t& b, float offset, man
 // box-box.  LDS scratch: 2 polygon buffers of 8 points (x,y,z) + 8 separations -> 56 slots,
 // [slot][64 lanes] (a quad clipped by 4 planes has at most 8 vertices)
 #define CLIP_SLOTS 56
-// STRIDE = distance (floats) between consecutive slots of one lane: 64 for [slot][64 lanes]
-// (k_narrow), 16 when the scratch of a 16-lane group lives inside its env's LDS area (k_solve16 fused)
+// STRIDE = distance (floats) between consecutive slots of one lane: 64 for [slot][64 lanes],
+// 16 when the scratch of a 16-lane group lives inside its env's LDS area (k_solve16 stage A, k_test_collide)
 template <int STRIDE>
 struct lds_poly {
   float* base;  // already offset by lane
@@ -191,8 +184,7 @@ MS_DEV int clip_poly(float* lds, int src, int n, f3 pn, float pd) {
       const float da = d[i], db = (i == 7 || wrap) ? d[0] : d[(i + 1) & 7];
       if (da <= 0.f && m < 8) out.put(m++, a);
       if (((da < 0.f && db > 0.f) || (da > 0.f && db < 0.f)) && m < 8) {
-        float t = da * rcp_safe(da - db);
-        out.put(m++, a + (b - a) * t);
+        out.put(m++, clip_cross(a, b, da, db));
       }
     }
   }

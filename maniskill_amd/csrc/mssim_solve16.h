@@ -446,8 +446,7 @@ MS_DEV void collide_box_box_coop(const shape_t& A, const shape_t& B, float offse
     const int pt = pa + (ea ? 1 : 0);
     if (ea && pa < 8) { scr[3 * pa] = P.x; scr[3 * pa + 1] = P.y; scr[3 * pa + 2] = P.z; }
     if (et && pt < 8) {
-      const float t = da * rcp_safe(da - db);
-      const f3 x = P + (b - P) * t;
+      const f3 x = clip_cross(P, b, da, db);
       scr[3 * pt] = x.x; scr[3 * pt + 1] = x.y; scr[3 * pt + 2] = x.z;
     }
     const int tot = __popc(ma) + __popc(mt);

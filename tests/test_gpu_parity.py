@@ -264,6 +264,41 @@ def test_pair_impulse_query_matches():
     assert torch.allclose(res[0][0], -res[0][1])
 
 
+def test_body_impulse_query_matches():
+    """`create_body_query` / `query_body_impulses`: HIP against the oracle, and on either backend a body's impulse is the signed
+    sum of the pair queries over every other row -- the static world (-1) included: half the cubes lie on the ground plane"""
+    model = panda_tabletop_model()
+    N = 128
+    gpu, cpu = make_pair(model, N)
+    r, t = model.row_of("cube"), model.row_of("table-workspace")
+    others = [-1] + [o for o in range(model.n_rows) if o != r]
+    cube = torch.zeros(N, 13)
+    cube[:, 2], cube[:, 3] = 0.02, 1.0
+    cube[: N // 2, :3] = torch.tensor([1.5, 0.0, -0.92 + 0.02])  # off the table, on the ground
+    res = []
+    for px in (gpu, cpu):
+        set_state(px, model, N, cube=cube)
+        qb = px.gpu_create_contact_body_impulse_query([r, t])
+        qp = px.gpu_create_contact_pair_impulse_query([(r, o) for o in others])
+        px.step(3)
+        px.gpu_query_contact_body_impulses(qb)
+        px.gpu_query_contact_pair_impulses(qp)
+        body = qb.cuda_impulses.torch().cpu().clone().reshape(2, N, 3)
+        pair = qp.cuda_impulses.torch().cpu().clone().reshape(len(others), N, 3)
+        # float32 sums of at most a few terms of 6e-3: 1e-8 covers the order of summation
+        assert torch.allclose(body[0], pair.sum(0), atol=1e-8, rtol=0)
+        assert torch.all(pair[0, : N // 2, 2] > 5e-3) and torch.all(pair[0, N // 2 :] == 0)  # the ground carries the first half
+        assert torch.equal(body[1, N // 2 :], -pair[others.index(t), N // 2 :]) and torch.all(body[1, : N // 2] == 0)
+        res.append(body)
+    w = 0.064 * 9.81 * 0.01  # cube weight: m g dt
+    assert torch.allclose(res[0][0, :, 2], torch.full((N,), w), rtol=2e-2)
+    assert torch.allclose(res[0][:, N // 2 :], res[1][:, N // 2 :], atol=2e-5)  # on the table: as the pair query above
+    # On the ground plane, whose frame (a quarter turn) is not exact in float32, the friction impulses of a cube at rest are
+    # rounding: the f32 oracle is 1.56e-5 from the f64 oracle there (1.2e-6 along the normal). Four times that.
+    assert torch.allclose(res[0][:, : N // 2], res[1][:, : N // 2], atol=6.3e-5)
+    assert torch.allclose(res[0][:, : N // 2, 2], res[1][:, : N // 2, 2], atol=5e-6)
+
+
 def test_link_jacobian_matches_oracle():
     """`mssim_link_jacobian` (HIP) against the oracle's, which tests/test_link_jacobian.py pins by finite differences"""
     model = panda_tabletop_model()
