@@ -162,3 +162,43 @@ def aba_forward_dynamics(rb: RobotDescription, q, qd, tau, gravity=(0, 0, -9.81)
         else:
             a[i] = ap
     return qdd
+
+
+def mass_matrix_and_bias(rb: RobotDescription, q, qd, gravity=(0, 0, -9.81), link_gravity=None, root_T=np.eye(4), armature=None):
+    """-> (M(q), c(q, qd)) with M qdd + c = tau, from the ABA above alone (no CRBA, no RNEA): column i of M^-1 is the
+    acceleration a unit torque on joint i gives at rest without gravity, aba(q, 0, e_i) - aba(q, 0, 0); the bias is what the
+    torque-free acceleration costs, c = -M aba(q, qd, 0), with the scene's gravity flags. `armature` (include/mssim.h
+    dof_armature: extra joint-space inertia) is added on M's diagonal; c belongs to the rigid-body part and is formed before it."""
+    q, qd = np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64)
+    n = len(q)
+    off = {l: False for l in rb.links}
+    z = np.zeros(n)
+    a0 = aba_forward_dynamics(rb, q, z, z, link_gravity=off, root_T=root_T)
+    Minv = np.stack([aba_forward_dynamics(rb, q, z, np.eye(n)[i], link_gravity=off, root_T=root_T) - a0 for i in range(n)], axis=1)
+    M = np.linalg.inv(Minv)
+    M = 0.5 * (M + M.T)
+    c = -M @ aba_forward_dynamics(rb, q, qd, z, gravity=gravity, link_gravity=link_gravity, root_T=root_T)
+    if armature is not None:
+        M = M + np.diag(np.asarray(armature, dtype=np.float64))
+    return M, c
+
+
+def link_point_jacobian(rb: RobotDescription, q, link, x, root_T=np.eye(4)):
+    """geometric Jacobian of the world point `x` carried by `link`: -> (Jv [3, n], Jw [3, n]). Column of a revolute joint on the
+    link's path to the root: axis x (x - p_joint) | axis; of a prismatic one: axis | 0; of every other joint: 0."""
+    names = active_joint_names(rb)
+    T = urdf_link_poses(rb, q, root_T)
+    Jv, Jw = np.zeros((3, len(names))), np.zeros((3, len(names)))
+    l = link
+    while l != rb.root:
+        j = rb.parent_joint[l]
+        if j.type != "fixed":
+            k = names.index(j.name)
+            axis = T[l][:3, :3] @ np.asarray(j.axis, dtype=np.float64)  # (the joint frame turns about / slides along its own axis)
+            if j.type == "prismatic":
+                Jv[:, k] = axis
+            else:
+                Jv[:, k] = np.cross(axis, np.asarray(x, dtype=np.float64) - T[l][:3, 3])
+                Jw[:, k] = axis
+        l = j.parent
+    return Jv, Jw

@@ -20,15 +20,17 @@ what the tests compare, are the bodies' velocities after the substep and the imp
 import numpy as np
 
 
-def lemke(M, q, max_iter=2000):
-    """w = M z + q >= 0, z >= 0, z.w = 0 by Lemke's algorithm with covering vector d = 1 (Cottle, Pang, Stone, algorithm 4.4.5)."""
+def lemke(M, q, max_iter=2000, d=None):
+    """w = M z + q >= 0, z >= 0, z.w = 0 by Lemke's algorithm with covering vector d > 0, 1 unless given (Cottle, Pang, Stone,
+    algorithm 4.4.5). A problem with one solution has it whatever d is: two runs with different d are a uniqueness check."""
     n = len(q)
     if np.all(q >= 0):
         return np.zeros(n)
+    d = np.ones(n) if d is None else np.asarray(d, dtype=np.float64)
     # tableau [I | -M | -d | q]: basis starts as w
-    T = np.hstack([np.eye(n), -M, -np.ones((n, 1)), q.reshape(-1, 1)]).astype(np.float64)
+    T = np.hstack([np.eye(n), -M, -d.reshape(-1, 1), q.reshape(-1, 1)]).astype(np.float64)
     basis = list(range(n))  # 0..n-1: w, n..2n-1: z, 2n: z0
-    r = int(np.argmin(q))
+    r = int(np.argmin(q / d))
     entering = 2 * n
 
     def pivot(row, col):
@@ -47,9 +49,21 @@ def lemke(M, q, max_iter=2000):
             raise RuntimeError("Lemke: ray termination")
         ratios = T[rows, -1] / col[rows]
         best = ratios.min()
-        ties = rows[ratios <= best + 1e-14]
-        # if z0 can leave, let it (the solution is reached)
-        row = next((i for i in ties if basis[i] == 2 * n), ties[0])
+        ties = rows[ratios <= best + 1e-14 + 1e-12 * abs(best)]
+        # if z0 can leave, let it (the solution is reached); other ties are broken lexicographically over the columns of the
+        # basis inverse (the w block of the tableau): no cycling on the degenerate problems coplanar points make
+        row = next((i for i in ties if basis[i] == 2 * n), None)
+        if row is None:
+            row = ties[0]
+            if len(ties) > 1:
+                cand = list(ties)
+                for k in range(n):
+                    vals = np.array([T[i, k] / col[i] for i in cand])
+                    keep = vals <= vals.min() + 1e-14
+                    cand = [i for i, kp in zip(cand, keep) if kp]
+                    if len(cand) == 1:
+                        break
+                row = cand[0]
         pivot(row, entering)
         leaving, basis[row] = basis[row], entering
         if leaving == 2 * n:
@@ -120,3 +134,130 @@ def solve_substep(bodies, contacts, dt, gravity=(0, 0, -9.81)):
         t1, t2 = tangents(n)
         imp[k] = lam_n[k] * np.asarray(n, float) + lam_t[2 * k] * t1 + lam_t[2 * k + 1] * t2
     return v.reshape(nb, 6), imp
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# One fixed-base articulation plus free bodies (restated here and not taken from the oracle).
+#
+# The velocity vector is u = [qd | 6 per free body]. The drives and the tendon are integrated implicitly, so the joint block
+# of the "mass" the constraint impulses act on is A = M + dt Kd + dt^2 Kp + w c c^T, and the free velocity of the joints is
+# A^-1 rhs. On top of the contact rows above there are unilateral joint-limit rows +-e_j with bias C / dt, and per patch one
+# torsional row -- relative spin about the patch normal -- written like a tangent axis (beta+, beta-, sigma) whose bound is
+# mu_t r times the SUM of the patch's normal multipliers.
+
+
+def joint_space_system(M, c, q, qd, dt, kp, kd, fmax, q_target, qd_target=None, qf=None, tendons=()):
+    """A qd* = rhs of the implicit drive integration with the one-pass force limit.
+    A = M + dt Kd + dt^2 Kp + sum w cc cc^T (w = dt^2 k + dt d per tendon (cc, offset, k, d): the constraint cc.q = offset),
+    rhs = M qd + dt (Kp (q_t - q) + Kd qd_t + tau_tendon - c + qf). Solved once; a joint whose implicit drive torque
+    kp (q_t - q - dt qd*) + kd (qd_t - qd*) exceeds fmax in size gets the constant +-fmax instead and loses dt kd + dt^2 kp;
+    the caller solves again. -> (A, rhs, saturated [n] bool)"""
+    q, qd, kp, kd, fmax, q_target = (np.asarray(a, dtype=np.float64) for a in (q, qd, kp, kd, fmax, q_target))
+    n = len(q)
+    qd_target = np.zeros(n) if qd_target is None else np.asarray(qd_target, dtype=np.float64)
+    qf = np.zeros(n) if qf is None else np.asarray(qf, dtype=np.float64)
+    base, tau_t = np.array(M, dtype=np.float64), np.zeros(n)
+    for cc, offset, k, d in tendons:
+        cc = np.asarray(cc, dtype=np.float64)
+        base += (dt * dt * k + dt * d) * np.outer(cc, cc)
+        tau_t -= k * (cc @ q - offset) * cc
+    implicit = dt * kd + dt * dt * kp
+    free_rhs = M @ qd + dt * (tau_t - np.asarray(c) + qf)
+    A = base + np.diag(implicit)
+    rhs = free_rhs + dt * (kp * (q_target - q) + kd * qd_target)
+    v = np.linalg.solve(A, rhs)
+    drive = kp * (q_target - q - dt * v) + kd * (qd_target - v)
+    sat = np.abs(drive) > fmax
+    A = base + np.diag(np.where(sat, 0.0, implicit))
+    rhs = np.where(sat, free_rhs + dt * np.sign(drive) * np.where(sat, fmax, 0.0), rhs)
+    return A, rhs, sat
+
+
+def solve_substep_generalized(A, rhs, link_jacobian, bodies, contacts, dt, limits=(), torsion=(), gravity=(0, 0, -9.81), covering=None):
+    """A, rhs: the joint-space system (joint_space_system); link_jacobian(link, x) -> (Jv, Jw) [3, n] each of the point x on `link`;
+    bodies: as in solve_substep; contacts: (a, b, x, n, gap, mu) where a side is a free-body index, -1 (fixed) or a link name;
+    limits: (joint, side = +-1, C >= 0): the row side * qd_j + C / dt >= 0;
+    torsion: (a, b, n, mu_t * r, [contact indices of the patch]): |torque about n| <= mu_t r sum lambda_n over those contacts.
+    -> (u+ [n + 6 nb], world impulse on side a per contact [nc, 3], info: z, w of the LCP, lam: the unilateral rows' multipliers,
+    sigma: per friction row the size of the relative velocity along it, M, q: the LCP itself, n_un, n_fr: its unilateral and friction row counts)"""
+    A = np.asarray(A, dtype=np.float64)
+    nq, nb, nc = A.shape[0], len(bodies), len(contacts)
+    nu = nq + 6 * nb
+    g = np.asarray(gravity, dtype=np.float64)
+    Minv = np.zeros((nu, nu))
+    ustar = np.zeros(nu)
+    if nq:
+        Minv[:nq, :nq] = np.linalg.inv(A)
+        ustar[:nq] = Minv[:nq, :nq] @ np.asarray(rhs, dtype=np.float64)
+    for i, B in enumerate(bodies):
+        o = nq + 6 * i
+        Minv[o : o + 3, o : o + 3] = np.eye(3) / B["m"]
+        Minv[o + 3 : o + 6, o + 3 : o + 6] = np.linalg.inv(B["I"])
+        acc = (g if B.get("gravity", True) else 0 * g) + np.asarray(B.get("f", np.zeros(3))) / B["m"]
+        ustar[o : o + 3] = np.asarray(B["v"]) + dt * acc
+        ustar[o + 3 : o + 6] = np.asarray(B["w"])
+
+    def row(a, b, x, lin, ang):
+        """relative velocity (a minus b) of the point x along `lin`, plus relative angular velocity along `ang`"""
+        J = np.zeros(nu)
+        for side, sgn in ((a, 1.0), (b, -1.0)):
+            if isinstance(side, str):
+                Jv, Jw = link_jacobian(side, x)
+                J[:nq] += sgn * (lin @ Jv + ang @ Jw)
+            elif side >= 0:
+                o = nq + 6 * side
+                J[o : o + 3] += sgn * lin
+                J[o + 3 : o + 6] += sgn * (np.cross(np.asarray(x) - bodies[side]["x"], lin) + ang)
+        return J
+
+    zero3 = np.zeros(3)
+    Ju = [row(a, b, x, np.asarray(n, float), zero3) for a, b, x, n, gap, mu in contacts]
+    bu = [gap / dt for a, b, x, n, gap, mu in contacts]
+    for j, side, C in limits:
+        e = np.zeros(nu)
+        e[j] = side
+        Ju.append(e)
+        bu.append(C / dt)
+    Jf = [row(a, b, x, t, zero3) for a, b, x, n, gap, mu in contacts for t in tangents(n)]
+    for a, b, n, mur, members in torsion:
+        Jf.append(row(a, b, zero3, zero3, np.asarray(n, float)))
+    n_un, n_fr = len(Ju), len(Jf)
+    Ju, Jf, bu = np.array(Ju).reshape(n_un, nu), np.array(Jf).reshape(n_fr, nu), np.array(bu)
+    bound = np.zeros((n_fr, n_un))  # friction row -> what its bound sums, with the coefficient
+    for k, c in enumerate(contacts):
+        bound[2 * k, k] = bound[2 * k + 1, k] = c[5]
+    for t, (a, b, n, mur, members) in enumerate(torsion):
+        bound[2 * nc + t, list(members)] = mur
+    # unknowns z = [lambda (n_un) | beta+ (n_fr) | beta- (n_fr) | sigma (n_fr)]
+    Auu, Auf, Aff = Ju @ Minv @ Ju.T, Ju @ Minv @ Jf.T, Jf @ Minv @ Jf.T
+    E, Z = np.eye(n_fr), np.zeros
+    Mlcp = np.block([
+        [Auu, Auf, -Auf, Z((n_un, n_fr))],
+        [Auf.T, Aff, -Aff, E],
+        [-Auf.T, -Aff, Aff, E],
+        [bound, -E, -E, Z((n_fr, n_fr))],
+    ])
+    qlcp = np.concatenate([Ju @ ustar + bu, Jf @ ustar, -(Jf @ ustar), np.zeros(n_fr)])
+    # Coplanar points make the problem degenerate and a pivot on rounding noise can end in a vector that is no solution: a
+    # result is taken only if it IS one (the checks below), else the pivoting starts again from another covering vector
+    rng = np.random.default_rng(len(qlcp))
+    z = None
+    for d in [covering] + [rng.uniform(0.5, 2.0, len(qlcp)) for _ in range(8)]:
+        try:
+            cand = lemke(Mlcp, qlcp, max_iter=20000, d=d)
+        except RuntimeError:
+            continue
+        w = Mlcp @ cand + qlcp
+        if cand.min() >= -1e-10 and w.min() >= -1e-9 and abs(cand @ w) < 1e-9:
+            z = np.maximum(cand, 0.0)
+            break
+    if z is None:
+        raise RuntimeError("Lemke: no covering vector led to a solution")
+    lam, lam_f = z[:n_un], z[n_un : n_un + n_fr] - z[n_un + n_fr : n_un + 2 * n_fr]
+    u = ustar + Minv @ (Ju.T @ lam + Jf.T @ lam_f)
+    imp = np.zeros((nc, 3))
+    for k, (a, b, x, n, gap, mu_k) in enumerate(contacts):
+        t1, t2 = tangents(n)
+        imp[k] = lam[k] * np.asarray(n, float) + lam_f[2 * k] * t1 + lam_f[2 * k + 1] * t2
+    sigma = z[n_un + 2 * n_fr :]  # per friction row: the size of the relative velocity along it (0: sticking)
+    return u, imp, dict(z=z, w=Mlcp @ z + qlcp, lam=lam, sigma=sigma, M=Mlcp, q=qlcp, n_un=n_un, n_fr=n_fr)
