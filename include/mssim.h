@@ -390,7 +390,11 @@ int MSSIM_FN(overflow_count)(mssim_handle h, void* stream);
  *   a = action[env][column[j]];  if (flags[j] & 2) a = low[j] + 0.5*(clip(a,-1,1)+1)*(high[j]-low[j]);
  *   target[j] = (flags[j] & 1 ? qpos[j] : 0) + a        (column[j] < 0: joint left untouched)
  *   flags[j] & 8: a is the joint's velocity drive target instead (pd_joint_vel.py:31-33); flags[j] & 4: the joint
- *   is driven by the end-effector block (set_ee_action_map)
+ *   is driven by the end-effector block (set_ee_action_map, or mssim_hip_tasks.h set_ee_ik_map)
+ *   flags[j] & 64: the joint is on the end-effector block's path and HELD by it -- it belongs to another controller (a
+ *   mobile base, a torso under the arm). The joint keeps its own row: column, bounds and the other flag bits act as
+ *   without the bit, which speaks to the two end-effector blocks alone. They use the joint in the forward kinematics
+ *   at its current position, leave its column out of J and write no target for it.
  *   flags[j] & 16 / & 32: a is multiplied by cos / sin of qpos[(flags[j] >> 8) & 31] -- the forward velocity of a planar
  *   base whose x, y and yaw are joints of the articulation, given in the base's own frame
  *   (agents/controllers/pd_base_vel.py:43-70: x joint: 16, y joint: 32, both on the forward column, yaw index in bits 8..12)
@@ -406,7 +410,7 @@ int MSSIM_FN(set_action_map)(mssim_handle h, const int32_t* column, const float*
  * vector) of link `link_index` in the root frame. flags & 2: translation clipped to [-1,1] and mapped to
  * [low, high]; rotation clipped by its norm to 1 and multiplied by rot_scale. The joints flagged 4 in
  * set_action_map get  target = qpos + J^T (J J^T + 1e-9 I)^-1 a,  J = Jacobian of the link over the joints on
- * its path, from the state of the last FK. link_index < 0 removes the block. */
+ * its path that are not flagged 64 (held), from the state of the last FK. link_index < 0 removes the block. */
 int MSSIM_FN(set_ee_action_map)(mssim_handle h, int32_t link_index, int32_t column0, int32_t rows, float low, float high, float rot_scale, int32_t flags);
 int MSSIM_FN(apply_action)(mssim_handle h, const float* action /* device [N][action_dim] */, int32_t action_dim, void* stream);
 /* apply_action followed by step(n_substeps) -- BaseEnv._step_action's set_action + substep loop

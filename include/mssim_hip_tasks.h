@@ -256,14 +256,17 @@ int64_t mssim_tail_step_count(mssim_handle h);
  *     mode 0: p = lin, q = euler_xyz(rot) (identity with 3 rows)
  *     mode 1: p = p_prev + lin, q = euler_xyz(rot) * q_prev (q_prev with 3 rows); no renormalisation
  * and solve, per env, a damped-least-squares IK of link `link_index` for that pose in the articulation's ROOT frame
- * over the joints on the link's path, from the visible qpos buffer:
+ * over the solved joints on the link's path (flagged 4), from the visible qpos buffer:
  *     repeat at most max_iters: err = target - FK(q) (6 rows: + rotation vector of q_t * conj(q_e));
  *       stop when max|err| < tolerance; step = J^T (J J^T + damping I)^-1 err, scaled so that max|step| <= max_step;
  *       q = clip(q + step, joint limits)
  * The exit is per env: an env's answer does not depend on the batch it is in. The result becomes the position target
- * (visible buffer and simulation state) of the path dofs, which must all be flagged 4 in set_action_map (call it
- * first) and number at most 8. A NaN in an env's columns or target gives NaN targets and a NaN target pose for that
- * env alone. The block runs as one launch after the joint-space map, followed by the step. Setting this block
+ * (visible buffer and simulation state) of the solved dofs. Every path dof must be flagged 4 (solved; at most 8) or 64
+ * (held: another controller's joint) in set_action_map (call it first). Held dofs enter the forward kinematics at
+ * their visible qpos, read once before the loop, have no column in J and get no target from the block; they must form a
+ * root-side prefix of the path (the Fetch: base x, y, yaw and torso before the seven arm joints), anything else is
+ * refused. A NaN in an env's columns or target gives NaN targets and a NaN target pose for that env alone; a NaN in
+ * its held positions gives NaN targets on its solved dofs alone. The block runs as one launch after the joint-space map, followed by the step. Setting this block
  * removes the one of set_ee_action_map and the other way round. */
 typedef struct mssim_ee_ik_map {
   int32_t link_index;     /* < 0 removes the block */
@@ -273,7 +276,8 @@ typedef struct mssim_ee_ik_map {
   int32_t max_iters; float damping, max_step, tolerance;   /* 60, 1e-3, 0.3, 1e-5; tolerance 0 = run exactly max_iters */
 } mssim_ee_ik_map;
 int mssim_set_ee_ik_map(mssim_handle h, const mssim_ee_ik_map* map, float* target_pose /* device [N][7] p, q(wxyz): read and written in place by every apply */);
-/* The solve alone, with the chain and settings of the block set last: q_out = q0 with the path dofs solved. */
+/* The solve alone, with the chain and settings of the block set last: q_out = q0 with the solved path dofs solved; held
+ * dofs are read from q0 and copied, as every dof off the path. */
 int mssim_ee_ik_solve(mssim_handle h, const float* target_pose /* [N][7] */, const float* q0 /* [N][n_dof] or NULL = visible qpos */,
                       float* q_out /* [N][n_dof]; dofs off the path copied from q0 */, int32_t* iters_out /* optional [N] */, void* stream);
 

@@ -192,11 +192,13 @@ class CombinedController(DictController):
         sub-controller cannot be expressed as an affine action -> target map. Fifth element: the end-effector block of
         `px.set_ee_action_map` or None. With an iterative-IK block (`px.set_ee_ik_map`) there is a sixth element,
         (link index, first action column, rows, mode, low, high, rot_scale, flags); its state tensor is
-        `fused_ik_target()`."""
+        `fused_ik_target()`. Joints on an end-effector block's path that other sub-controllers own keep their rows and get
+        bit 64 on top: held by the block (include/mssim.h `set_action_map`)."""
         n = self.articulation.max_dof
         col, lo, hi, fl = [-1] * n, [0.0] * n, [0.0] * n, [0] * n
         ee = None  # end-effector block: (link index, first action column, rows, low, high, rot_scale, flags)
         ik, self._fused_ik_controller = None, None
+        held = []
         for uid, c in self.controllers.items():
             spec = getattr(c, "fused_action_spec", lambda: None)()
             if spec is None:
@@ -213,9 +215,12 @@ class CombinedController(DictController):
                     ee = (link, start, rows, l, h, rs, f)
                 for dof in spec["dofs"]:
                     fl[dof] = 4  # driven by the end-effector block
+                held = spec.get("held", [])
                 continue
             for dof, lcol, l, h, f in spec:
                 col[dof], lo[dof], hi[dof], fl[dof] = start + lcol, l, h, f
+        for dof in held:  # (after every sub-controller has written its rows)
+            fl[dof] |= 64
         return (col, lo, hi, fl, ee) if ik is None else (col, lo, hi, fl, ee, ik)
 
     def fused_ik_target(self):

@@ -44,7 +44,8 @@ class PDEEPosController(PDJointPosController):
         """the delta controllers (`pd_ee_delta_pos`, `pd_ee_delta_pose`) are one pseudo-inverse step of the
         commanded translation (and rotation vector): the native action map has an end-effector block for
         exactly that (include/mssim.h `set_ee_action_map`). Returns {"ee": (link index, rows, low, high,
-        rot_scale, flags), "dofs": [...]}.
+        rot_scale, flags), "dofs": [...], "held": [...]}; `held` lists the joints on the link's path that belong to other
+        controllers (the Fetch's base and torso): the block leaves them where they are.
         The modes that track a target pose (`pd_ee_target_delta_pos`, `pd_ee_target_delta_pose`: use_target with
         use_delta; `pd_ee_pose`: the absolute pose) have the iterative-IK block (include/mssim_hip_tasks.h
         `set_ee_ik_map`): {"ik": (link index, rows, mode, low, high, rot_scale, flags), "dofs": [...]}, mode 0 absolute,
@@ -71,16 +72,23 @@ class PDEEPosController(PDJointPosController):
             if not np.all(rl == rl[0]):
                 return None
             rot_scale = float(rl[0])
-        if set(self.kinematics.active_ancestor_joint_idxs) != set(int(i) for i in self.active_joint_indices.tolist()):
-            return None  # the step moves every joint on the link's path: they must all be this controller's
-        flags = 2 if self._normalize_action else 0
+        path = self.kinematics.active_ancestor_joint_idxs
         dofs = [int(i) for i in self.active_joint_indices.tolist()]
+        if not set(dofs) <= set(path):
+            return None  # the block writes targets of joints on the link's path only
+        # path joints of other controllers are held (bit 64 of their rows in the joint map): they keep their own targets
+        held = [j for j in path if j not in dofs]
+        if held and not self.scene.px.supports_fused_callers:
+            return None  # (bit 64 is the HIP library's: no other backend has an action map that knows it)
+        flags = 2 if self._normalize_action else 0
         if tracked:
             if len(dofs) > 8:
-                return None  # the iterative-IK kernel keeps a chain of at most 8 joints in registers
-            return dict(ik=(self.kinematics.end_link_idx, 6 if pose else 3, 1 if cfg.use_delta else 0, float(lo[0]), float(hi[0]), rot_scale, flags), dofs=dofs)
+                return None  # the iterative-IK kernel keeps a chain of at most 8 solved joints in registers
+            if path[: len(held)] != held:
+                return None  # ... and composes the held joints once, as the chain's root-side prefix
+            return dict(ik=(self.kinematics.end_link_idx, 6 if pose else 3, 1 if cfg.use_delta else 0, float(lo[0]), float(hi[0]), rot_scale, flags), dofs=dofs, held=held)
         return dict(ee=(self.kinematics.end_link_idx, 6 if pose else 3, float(lo[0]), float(hi[0]), rot_scale, flags),
-                    dofs=dofs)
+                    dofs=dofs, held=held)
 
     def fused_ik_target(self):
         """the [N, 7] float32 target pose (root frame) that the iterative-IK block reads and updates in place: the very

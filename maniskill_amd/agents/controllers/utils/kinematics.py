@@ -45,6 +45,10 @@ class Kinematics:
         self.controlled_joints_idx_in_qmask = [self.active_ancestor_joint_idxs.index(int(i)) for i in active_joint_indices]
         self.qmask = torch.zeros(len(self.active_ancestor_joints), dtype=torch.bool, device=self.device)
         self.qmask[self.controlled_joints_idx_in_qmask] = True
+        # path joints the controller does not own are HELD: they take part in the forward kinematics at their current
+        # positions, contribute no Jacobian column and get no target (the reference's CPU branch: active_qmask=self.qmask)
+        self.solved_joint_idxs: List[int] = [int(i) for i in active_joint_indices]
+        self.held_joint_idxs: List[int] = [j for j in self.active_ancestor_joint_idxs if j not in self.solved_joint_idxs]
         self.use_gpu_ik = True
         self._chain = None
 
@@ -101,12 +105,15 @@ class Kinematics:
 
     # ------------------------------------------------------------------ IK
     def compute_ik(self, target_pose: Pose, q0: torch.Tensor, pos_only: bool = False, action=None, use_delta_ik_solver: bool = False):
-        """Target joint positions of the chain joints for an end-link target pose given in the ROOT frame
-        (same contract as the reference, kinematics.py:124-186)."""
-        q0 = q0[:, self.active_ancestor_joint_idxs]
+        """Target joint positions [B, len(active_joint_indices)] of the controller's own joints, in its joint order, for
+        an end-link target pose given in the ROOT frame (the reference's CPU branch, kinematics.py:174-186). Path joints
+        of other controllers are held where `q0` has them."""
+        held = len(self.held_joint_idxs) > 0
         if use_delta_ik_solver:
-            # one pseudo-inverse step of the commanded delta (Buss, "Introduction to inverse kinematics")
-            J = self.articulation.px.link_jacobian(self.end_link_idx)[:, :, self.active_ancestor_joint_idxs]
+            # one pseudo-inverse step of the commanded delta (Buss, "Introduction to inverse kinematics") over the
+            # solved joints' columns (without a held joint: all columns of the path)
+            q0 = q0[:, self.solved_joint_idxs if held else self.active_ancestor_joint_idxs]
+            J = self.articulation.px.link_jacobian(self.end_link_idx)[:, :, self.solved_joint_idxs if held else self.active_ancestor_joint_idxs]
             if pos_only:
                 J = J[:, 0:3]
             # J^+ a = J^T (J J^T)^-1 a for the full-row-rank J of a 7-joint arm (what pinv returns away
@@ -116,12 +123,16 @@ class Kinematics:
             JJt = JJt + 1e-9 * torch.eye(JJt.shape[1], device=J.device)
             return q0 + (J.transpose(1, 2) @ torch.linalg.solve(JJt, action.unsqueeze(-1))).squeeze(-1)
         # damped least squares on the pose error (own solver, see module docstring)
+        q0 = q0[:, self.active_ancestor_joint_idxs]
         tp, tq = target_pose.p, target_pose.q
         q = q0.clone()
+        sel = self.controlled_joints_idx_in_qmask  # the solved joints' places in the path, in the controller's order
         lam = 1e-3
         if self._chain is None:
             self._build_chain()
         lo, hi = self._chain["lim"][:, 0], self._chain["lim"][:, 1]
+        if held:
+            lo, hi = lo[sel], hi[sel]
         conj = torch.tensor([1.0, -1.0, -1.0, -1.0], device=q.device)
         for _ in range(60):
             pe, qe, J = self.fk_jacobian(q)
@@ -134,10 +145,16 @@ class Kinematics:
                 err = torch.cat((err, dq[:, 1:] / nv.clamp_min(1e-9) * ang), 1)  # rotation vector of the remaining turn
             else:
                 J = J[:, :3]
+            if held:
+                J = J[:, :, sel]
             if float(err.abs().max()) < 1e-5:
                 break
             JJt = J @ J.transpose(1, 2) + lam * torch.eye(J.shape[1], device=q.device)
             step = (J.transpose(1, 2) @ torch.linalg.solve(JJt, err.unsqueeze(-1))).squeeze(-1)
             step = step * (0.3 / step.abs().amax(dim=1, keepdim=True).clamp_min(0.3))  # at most 0.3 rad per joint per iteration
-            q = torch.minimum(torch.maximum(q + step, lo), hi)
-        return q
+            if held:  # only the solved entries move, against their own limits
+                q = q.clone()
+                q[:, sel] = torch.minimum(torch.maximum(q[:, sel] + step, lo), hi)
+            else:
+                q = torch.minimum(torch.maximum(q + step, lo), hi)
+        return q[:, sel] if held else q

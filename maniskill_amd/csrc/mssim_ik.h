@@ -4,10 +4,10 @@
 //
 // Per env, what agents/controllers/utils/kinematics.py `compute_ik` does in its iterative branch for that env alone:
 //
-//   q = q0[path]
+//   q = q0[solved]; (p0, r0) = the held joints of the path composed at q0[held] (identity without one)
 //   repeat at most max_iters:
-//     (pe, qe, J) = FK + geometric Jacobian of the link over the dofs on its path, in the ROOT frame, from the chain's
-//                   constant tables (never the root pose or the simulation's body poses)
+//     (pe, qe, J) = FK + geometric Jacobian of the link over the solved dofs on its path, in the ROOT frame, from
+//                   (p0, r0) and the chain's constant tables (never the root pose or the simulation's body poses)
 //     err = tp - pe ; rows == 6: append the rotation vector of tq * conj(qe) (w >= 0, angle = 2 atan2(|v|, w))
 //     if max|err| < tolerance: stop                       <- this env only
 //     step = J^T (J J^T + damping I)^-1 err               (rows x rows SPD: Cholesky without pivoting)
@@ -19,17 +19,26 @@
 // an env stops at its own convergence: its answer is a function of its own inputs alone (the first envs of a large
 // batch are bit-identical to a small batch), and a torch call with a batch of one is the same algorithm.
 //
+// HELD JOINTS. A path joint flagged 64 in the joint map (include/mssim.h) belongs to another controller: it takes part
+// in the forward kinematics where it is, has no Jacobian column and gets no target. The held joints form a root-side
+// prefix of the path (the Fetch: base x, y, yaw and the torso before the seven arm joints), so each lane composes them
+// once, before the loop, into one transform (p0, r0) from which the solved chain starts; the loop itself is the one of a
+// chain without held joints. k_ee_ik<ROWS, false> is that chain's kernel, instruction for instruction what it was
+// before held joints existed; k_ee_ik<ROWS, true> starts from (p0, r0). A NaN held position makes (p0, r0) NaN, hence
+// every solved joint of that env, as a NaN target does.
+//
 // Layout: 64-thread blocks, one env per lane; a wave ends with its slowest lane. The chain's constants (at most
 // MSSIM_IK_MAX_JOINTS joints) come by value in the kernel arguments: wave-uniform, read with scalar loads. Every loop
 // over joints and rows is unrolled to its compile-time maximum under a uniform `k < n` guard, so q, the Jacobian and
 // the Cholesky factor stay in registers. sincosf / atan2f / sqrtf are the precise library versions.
 #pragma once
 
-#define MSSIM_IK_MAX_JOINTS 8
+#define MSSIM_IK_MAX_JOINTS 8  // solved
+#define MSSIM_IK_MAX_HELD 15   // held: an articulation has at most 16 dofs and one of them is solved
 
 struct IkChain {
   int link;   // < 0: no block
-  int n;      // joints on the link's path, root side first
+  int n;      // solved joints on the link's path, root side first
   int rows;   // 3: position, 6: position + orientation
   int col0, mode, flags;
   float lo, hi, rot_scale;
@@ -41,6 +50,11 @@ struct IkChain {
   float axis[MSSIM_IK_MAX_JOINTS][3];
   float lower[MSSIM_IK_MAX_JOINTS], upper[MSSIM_IK_MAX_JOINTS];
   float tip[7];                          // last body -> link frame, unit quaternion
+  int n_held;                            // held joints: the path's root-side prefix, before dof[0]
+  int held_dof[MSSIM_IK_MAX_HELD];
+  unsigned held_revolute;                // bit k: held joint k is revolute
+  float held_frame[MSSIM_IK_MAX_HELD][7];
+  float held_axis[MSSIM_IK_MAX_HELD][3];
 };
 
 // v rotated by the unit quaternion q: v + w t + u x t, t = 2 u x v
@@ -50,15 +64,15 @@ MS_DEV f3 ik_qrot(q4 q, f3 v) {
   return v + t * q.w + cross(u, t);
 }
 
-// the loop above on q[0 .. C.n); returns the number of steps taken
-template <int ROWS>
-MS_DEV int ik_solve(const IkChain& C, f3 tp, q4 tq, float (&q)[MSSIM_IK_MAX_JOINTS]) {
+// the loop above on q[0 .. C.n), the chain starting at (p0, r0) (HELD; else at the root); returns the number of steps taken
+template <int ROWS, bool HELD>
+MS_DEV int ik_solve(const IkChain& C, f3 tp, q4 tq, float (&q)[MSSIM_IK_MAX_JOINTS], f3 p0, q4 r0) {
   constexpr int MJ = MSSIM_IK_MAX_JOINTS;
   int it = 0;
   for (;;) {
     // ---- FK down the chain: world axis and anchor of every joint
-    f3 p = f3{0.f, 0.f, 0.f};
-    q4 r = q4{1.f, 0.f, 0.f, 0.f};
+    f3 p = HELD ? p0 : f3{0.f, 0.f, 0.f};
+    q4 r = HELD ? r0 : q4{1.f, 0.f, 0.f, 0.f};
     f3 ax[MJ], an[MJ];
 #pragma unroll
     for (int k = 0; k < MJ; k++) {
@@ -172,8 +186,8 @@ MS_DEV int ik_solve(const IkChain& C, f3 tp, q4 tq, float (&q)[MSSIM_IK_MAX_JOIN
 
 // The two forms of one launch. Map form (`action` set; runs right after k_apply_action): the block's columns ->
 // target pose (updated in place) -> joint targets of the path dofs flagged 4, in the visible buffer and the simulation
-// state, started from the visible qpos. Solve form (`action` null): q_out = q0 with the path dofs solved for
-// target_pose; q0 null: the visible qpos buffer (else the simulation's own). Both are the same kernel, so the same
+// state, started from the visible qpos. Solve form (`action` null): q_out = q0 with the solved path dofs solved for
+// target_pose (held and off-path dofs are q0's bits); q0 null: the visible qpos buffer (else the simulation's own). Both are the same kernel, so the same
 // inputs give the same bits in either form.
 struct IkIo {
   const float* action; int adim; const int* flags;  // map form
@@ -181,7 +195,10 @@ struct IkIo {
   const float* q0; float* q_out; int* iters_out;    // solve form
 };
 
-template <int ROWS>
+// (the chain travels by value: the whole argument block stays well under the 4 KB a launch may carry)
+static_assert(sizeof(IkChain) + sizeof(DevState) + sizeof(mssim_buffers) + sizeof(IkIo) + 64 <= 3072, "k_ee_ik's kernel arguments");
+
+template <int ROWS, bool HELD>
 __global__ __launch_bounds__(64) void k_ee_ik(IkChain C, DevState S, mssim_buffers B, int n_dof, IkIo io) {
   const int N = S.N;
   const int e = xcd_chunk(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
@@ -223,7 +240,25 @@ __global__ __launch_bounds__(64) void k_ee_ik(IkChain C, DevState S, mssim_buffe
   float q[MSSIM_IK_MAX_JOINTS];
 #pragma unroll
   for (int k = 0; k < MSSIM_IK_MAX_JOINTS; k++) q[k] = k < C.n ? start(C.dof[k]) : 0.f;
-  const int it = ik_solve<ROWS>(C, tp, tq, q);
+  // the held prefix at its current positions, composed once: joint frame, then the joint's own motion
+  f3 p0 = f3{0.f, 0.f, 0.f};
+  q4 r0 = q4{1.f, 0.f, 0.f, 0.f};
+  if (HELD) {
+    for (int k = 0; k < C.n_held; k++) {
+      const float qk = start(C.held_dof[k]);
+      const f3 jp = p0 + ik_qrot(r0, f3{C.held_frame[k][0], C.held_frame[k][1], C.held_frame[k][2]});
+      const q4 jq = qmul(r0, q4{C.held_frame[k][3], C.held_frame[k][4], C.held_frame[k][5], C.held_frame[k][6]});
+      const f3 axis = f3{C.held_axis[k][0], C.held_axis[k][1], C.held_axis[k][2]};
+      if ((C.held_revolute >> k) & 1u) {
+        float s, c;
+        sincosf(0.5f * qk, &s, &c);
+        p0 = jp; r0 = qmul(jq, q4{c, s * axis.x, s * axis.y, s * axis.z});
+      } else {
+        p0 = jp + ik_qrot(jq, axis) * qk; r0 = jq;
+      }
+    }
+  }
+  const int it = ik_solve<ROWS, HELD>(C, tp, tq, q, p0, r0);
 #pragma unroll
   for (int k = 0; k < MSSIM_IK_MAX_JOINTS; k++)
     if (k < C.n) {

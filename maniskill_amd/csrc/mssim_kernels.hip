@@ -377,7 +377,8 @@ __global__ void k_query(DevModel M, DevState S, const int* q, int nq, int body_q
 
 // End-effector block of the action map (pd_ee_delta_pos): 3 action columns = translation of link `link` in the
 // root frame; the joints flagged 4 in the joint map get  target = qpos + J^T (J J^T + 1e-9 I)^-1 a  with J the
-// translational Jacobian of the link over all joints on its path (agents/controllers/utils/kinematics.py:156-171)
+// translational Jacobian of the link over the joints on its path that are not flagged 64 (held: another controller's
+// joints, which stay where they are; agents/controllers/utils/kinematics.py `compute_ik`)
 struct EeMap {
   int link;    // < 0: no end-effector block
   int col0;    // first action column
@@ -454,7 +455,7 @@ __global__ void k_apply_action(DevModel M, DevState S, mssim_buffers B, const fl
     if (ee.rows == 3) {
       s3 G = s3{1e-9f, 1e-9f, 1e-9f, 0.f, 0.f, 0.f};  // xx yy zz xy xz yz
       for (int j = 0; j < n; j++)
-        if ((path >> j) & 1u) {
+        if (((path >> j) & 1u) && !(flags[j] & 64)) {
           f3 w;
           const f3 v = jcol(j, w);
           G.xx += v.x * v.x; G.yy += v.y * v.y; G.zz += v.z * v.z; G.xy += v.x * v.y; G.xz += v.x * v.z; G.yz += v.y * v.z;
@@ -471,7 +472,7 @@ __global__ void k_apply_action(DevModel M, DevState S, mssim_buffers B, const fl
 #pragma unroll
         for (int q = 0; q < 6; q++) G[r][q] = r == q ? 1e-9f : 0.f;
       for (int j = 0; j < n; j++)
-        if ((path >> j) & 1u) {
+        if (((path >> j) & 1u) && !(flags[j] & 64)) {
           f3 w;
           const f3 v = jcol(j, w);
           const float cj[6] = {v.x, v.y, v.z, w.x, w.y, w.z};
@@ -1677,12 +1678,17 @@ static int check_action_dim(mssim_handle h, int32_t action_dim) {
   }
   return 0;
 }
+// the iterative-IK launch, either form: a chain with held joints starts from their composed transform (mssim_ik.h)
+static void launch_ee_ik(mssim_handle h, const IkIo& io, hipStream_t st) {
+  auto k = h->ik.n_held > 0 ? (h->ik.rows == 6 ? k_ee_ik<6, true> : k_ee_ik<3, true>) : (h->ik.rows == 6 ? k_ee_ik<6, false> : k_ee_ik<3, false>);
+  hipLaunchKernelGGL(k, env_grid(h->N, 64), dim3(64), 0, st, h->ik, h->S, h->buf, h->M.n_dof, io);
+}
 static void launch_apply_action(mssim_handle h, const float* action, int action_dim, hipStream_t st) {
   hipLaunchKernelGGL(k_apply_action, env_grid(h->N, 256), dim3(256), 0, st, h->M, h->S, h->buf, action, action_dim,
                      h->d_act_col, h->d_act_lo, h->d_act_hi, h->d_act_flags, h->ee);
   if (h->ik.link >= 0) {  // the joint-space rows are written; the iterative-IK block follows in a launch of its own
     const IkIo io{action, action_dim, h->d_act_flags, h->ik_target_pose, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(h->ik.rows == 6 ? k_ee_ik<6> : k_ee_ik<3>, env_grid(h->N, 64), dim3(64), 0, st, h->ik, h->S, h->buf, h->M.n_dof, io);
+    launch_ee_ik(h, io, st);
   }
 }
 static int step_action_now(mssim_handle h, const float* action, int32_t action_dim, int32_t n_substeps, hipStream_t st) {
@@ -1819,29 +1825,49 @@ int mssim_set_ee_ik_map(mssim_handle h, const mssim_ee_ik_map* map, float* targe
   std::vector<int> path;
   for (int b = link_body[map->link_index]; b >= 0; b = parent[b]) path.insert(path.begin(), b);
   if (path.empty()) { h->err = "set_ee_ik_map: the link has no joint on its path"; return 1; }
-  if ((int)path.size() > MSSIM_IK_MAX_JOINTS) {
-    h->err = "set_ee_ik_map: the link has " + std::to_string(path.size()) + " joints on its path, the iterative IK takes at most " + std::to_string(MSSIM_IK_MAX_JOINTS);
+  // every path joint is solved (flagged 4) or held (flagged 64: another controller's, kept where it is)
+  std::vector<int> solved, held;
+  for (int j : path) {
+    if (flags[j] & 4) solved.push_back(j);
+    else if (flags[j] & 64) held.push_back(j);
+    else { h->err = "set_ee_ik_map: dof " + std::to_string(j) + " is on the link's path but not flagged 4 in the joint map"; return 1; }
+  }
+  if ((int)solved.size() > MSSIM_IK_MAX_JOINTS) {
+    h->err = "set_ee_ik_map: the link has " + std::to_string(solved.size()) + " joints" + (held.empty() ? "" : " flagged 4") + " on its path, the iterative IK takes at most " + std::to_string(MSSIM_IK_MAX_JOINTS);
     return 1;
   }
-  for (int j : path)
-    if (!(flags[j] & 4)) { h->err = "set_ee_ik_map: dof " + std::to_string(j) + " is on the link's path but not flagged 4 in the joint map"; return 1; }
+  if (solved.empty()) { h->err = "set_ee_ik_map: every joint on the link's path is held (flagged 64), none is left to solve for"; return 1; }
+  for (size_t k = 0; k < held.size(); k++)
+    if (path[k] != held[k]) {
+      h->err = "set_ee_ik_map: dof " + std::to_string(held[k]) + " is held (flagged 64) behind a solved joint: the held joints must be a root-side prefix of the link's path";
+      return 1;
+    }
+  if ((int)held.size() > MSSIM_IK_MAX_HELD) { h->err = "set_ee_ik_map: more than " + std::to_string(MSSIM_IK_MAX_HELD) + " held joints on the link's path"; return 1; }
   auto unit7 = [](const float* src, float* dst) {  // the quaternion normalised in double, as the reference does
     const double w = src[3], x = src[4], y = src[5], z = src[6], n = std::sqrt(w * w + x * x + y * y + z * z);
     for (int c = 0; c < 3; c++) dst[c] = src[c];
     dst[3] = (float)(w / n); dst[4] = (float)(x / n); dst[5] = (float)(y / n); dst[6] = (float)(z / n);
   };
   IkChain c{};
-  c.link = map->link_index; c.n = (int)path.size(); c.rows = map->rows; c.col0 = map->column0; c.mode = map->mode; c.flags = map->flags;
+  c.link = map->link_index; c.n = (int)solved.size(); c.rows = map->rows; c.col0 = map->column0; c.mode = map->mode; c.flags = map->flags;
   c.lo = map->low; c.hi = map->high; c.rot_scale = map->rot_scale;
   c.max_iters = map->max_iters; c.damping = map->damping; c.max_step = map->max_step; c.tol = map->tolerance;
   for (int k = 0; k < c.n; k++) {
-    const int j = path[k];
+    const int j = solved[k];
     c.dof[k] = j; c.revolute[k] = type[j] == MSSIM_JOINT_REVOLUTE;
     unit7(&frame[7 * (size_t)j], c.frame[k]);
     for (int a = 0; a < 3; a++) c.axis[k][a] = axis[3 * (size_t)j + a];
     c.lower[k] = limit[2 * (size_t)j]; c.upper[k] = limit[2 * (size_t)j + 1];
   }
   unit7(&link_frame[7 * (size_t)map->link_index], c.tip);
+  c.n_held = (int)held.size();
+  for (int k = 0; k < c.n_held; k++) {
+    const int j = held[k];
+    c.held_dof[k] = j;
+    if (type[j] == MSSIM_JOINT_REVOLUTE) c.held_revolute |= 1u << k;
+    unit7(&frame[7 * (size_t)j], c.held_frame[k]);
+    for (int a = 0; a < 3; a++) c.held_axis[k][a] = axis[3 * (size_t)j + a];
+  }
   h->ik = c;
   h->ik_target_pose = target_pose;
   h->ee.link = -1;  // the two end-effector blocks exclude each other
@@ -1853,7 +1879,7 @@ int mssim_ee_ik_solve(mssim_handle h, const float* target_pose, const float* q0,
   if (h->ik.link < 0) { h->err = "ee_ik_solve: set_ee_ik_map has not been called"; return 1; }
   if (!target_pose || !q_out) { h->err = "ee_ik_solve: no target_pose / q_out"; return 1; }
   const IkIo io{nullptr, 0, nullptr, const_cast<float*>(target_pose), q0, q_out, iters_out};  // (read only in this form)
-  hipLaunchKernelGGL(h->ik.rows == 6 ? k_ee_ik<6> : k_ee_ik<3>, env_grid(h->N, 64), dim3(64), 0, (hipStream_t)stream, h->ik, h->S, h->buf, h->M.n_dof, io);
+  launch_ee_ik(h, io, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -66,6 +66,13 @@ for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("Pe
                  (("PlaceSphere-v1", 4096), {}), (("PullCubeTool-v1", 4096), {}),
                  (("PickCube-v1", 4096), dict(sim_config=dict(control_freq=25))),  # 4 substeps (SURVEY 8d reports 5 and 4)
                  # BASELINE config 5's robot and env count: the Fetch on an empty ground, and in synthetic triangle-mesh rooms
-                 (("Empty-v1", 1024), dict(robot_uids="fetch")), (("SceneManipulation-v1", 1024), dict(build_config_idxs=[i % 5 for i in range(1024)]))):
-    if not only or args[0] in only or kw.get("control_mode") in only or ("substeps4" in only and "sim_config" in kw):
+                 (("Empty-v1", 1024), dict(robot_uids="fetch")), (("SceneManipulation-v1", 1024), dict(build_config_idxs=[i % 5 for i in range(1024)])),
+                 # the Fetch's end-effector modes: base and torso are on the gripper's path and held by the two blocks
+                 # (`fetch_ee` selects these four rows alone; MS_FUSED=0: the torch solver)
+                 *((("Empty-v1", 1024), dict(robot_uids="fetch", control_mode=m))
+                   for m in ("pd_ee_delta_pos", "pd_ee_delta_pose", "pd_ee_target_delta_pos", "pd_ee_target_delta_pose"))):
+    fetch_ee = kw.get("robot_uids") == "fetch" and "control_mode" in kw
+    if "fetch_ee" in only and not fetch_ee:
+        continue
+    if not only or args[0] in only or kw.get("control_mode") in only or ("substeps4" in only and "sim_config" in kw) or ("fetch_ee" in only and fetch_ee):
         run(*args, **kw)
