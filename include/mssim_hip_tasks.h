@@ -244,6 +244,33 @@ typedef struct mssim_pulltool_task {
 
 int mssim_task_pulltool_outputs(mssim_handle h, const mssim_pulltool_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream);
 
+/* The robot-dependent rules of the task epilogues, stored on the handle: what "the robot is static" means and how many
+ * joints the velocity norm of PickCube's static reward covers. With no profile set (or after a NULL / n_ranges == 0 call)
+ * every epilogue applies the Panda's rules from its own task struct, as before: static = max |qvel[:n_static_dofs]| <=
+ * static_thresh, norm over qvel[:n_static_dofs].
+ * With a profile set, the separate-launch epilogues that read the robot's velocities (pick, poke, place) use instead
+ *     static = for every range r < n_ranges and every joint j in [first[r], first[r] + count[r]):
+ *                  (signed_compare ? qvel[j] : |qvel[j]|) <= thresh[r]
+ *     PickCube's static reward: 1 - tanh 5 |qvel[:pick_norm_dofs]|  (the other tasks keep their n_static_dofs)
+ * and the task struct's static_thresh / robot_static_thresh is not read. The Fetch (agents/robots/fetch/fetch.py
+ * is_static): ranges {0, 3, 0.05} (the base) and {3, n - 5, threshold} (body and arm), signed_compare = 1 -- a joint moving
+ * fast in the negative direction counts as static, as in the torch path -- and pick_norm_dofs = n (pick_cube.py slices
+ * the two finger joints off for "panda" only).
+ * The grasp rule needs no entry here: the epilogues test the force on finger1_row against +y of that link and the force on
+ * finger2_row against -y; a robot whose fingers close the other way round (the Fetch: -y of the left finger, +y of the
+ * right) hands its right finger in as finger 1 and its left as finger 2.
+ * The control-step kernel's tail epilogues never read the profile: while one is set, every epilogue of the handle runs as
+ * a launch of its own. Refused (rc 3): n_ranges outside [0, 2], a range outside [0, n_dof), pick_norm_dofs outside
+ * [0, n_dof], a threshold that is NaN. A null handle returns 1. */
+typedef struct mssim_task_robot {
+  int32_t n_ranges;            /* 0 (no profile), 1 or 2 */
+  int32_t first[2], count[2];  /* joint ranges, within [0, n_dof) */
+  float thresh[2];
+  int32_t signed_compare;      /* 0: |qvel| <= thresh, 1: qvel <= thresh */
+  int32_t pick_norm_dofs;      /* leading joints of PickCube's reward norm, in [0, n_dof] */
+} mssim_task_robot;
+int mssim_set_task_robot(mssim_handle h, const mssim_task_robot* robot);
+
 /* How many control steps of this handle so far ran as one launch with a task epilogue at the control-step kernel's
  * tail (a deferred step_action + fetch consumed by a task_*_outputs call), against the separate epilogue launch.
  * A host counter: no sync. */

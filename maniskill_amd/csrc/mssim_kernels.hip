@@ -521,6 +521,22 @@ __global__ void k_apply_action(DevModel M, DevState S, mssim_buffers B, const fl
 
 #include "mssim_ik.h"  // iterative IK block of the action map (the end-effector modes that track a target pose)
 
+// The robot's is_static under a robot profile (mssim_set_task_robot, R.n_ranges > 0), as the static threshold of a task
+// struct that makes the per-env function below decide the same: +inf where the robot is static, -1 where it is not (the
+// functions test max |qvel| <= threshold, and that maximum is never NaN). qvel: the env's row of the visible buffer. The
+// comparison is signed where the profile says so (Fetch.is_static: a joint moving fast in the negative direction counts as
+// static); a NaN velocity is not static under either. The per-env functions themselves do not know of the profile: the
+// tail instances of k_solve16 compile them as before, and so does every k_task_*<FETCH, false>.
+MS_DEV float profile_static_thresh(const mssim_task_robot& R, const float* __restrict__ qvel) {
+  bool is_static = true;
+  for (int r = 0; r < R.n_ranges; r++)
+    for (int j = R.first[r]; j < R.first[r] + R.count[r]; j++) {
+      const float v = qvel[j];
+      is_static = is_static && (R.signed_compare ? v : fabsf(v)) <= R.thresh[r];
+    }
+  return is_static ? INFINITY : -1.f;
+}
+
 // PickCube-style evaluate / obs / reward
 // FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
 MS_DEV void task_pick_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_pick_task& T, const int* __restrict__ pairs, int npairs,
@@ -589,12 +605,17 @@ MS_DEV void task_pick_env(const DevModel& M, const DevState& S, const mssim_buff
   if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
 }
 // FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
-template <bool FETCH>
+// PROFILE: the handle has a robot profile R: its static rule decides, and the reward's velocity norm covers R.pick_norm_dofs joints
+template <bool FETCH, bool PROFILE>
 __global__ __launch_bounds__(256) void k_task_pick(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_pick_task T, const int* __restrict__ pairs, int npairs,
-                                                    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags) {
+                                                    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, mssim_task_robot R) {
   int e;
   if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
   else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  if constexpr (PROFILE) {
+    T.static_thresh = profile_static_thresh(R, B.art_qvel + (size_t)e * M.n_dof);
+    T.n_static_dofs = R.pick_norm_dofs;
+  }
   task_pick_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
 }
 
@@ -1000,12 +1021,15 @@ MS_DEV void task_poke_env(const DevModel& M, const DevState& S, const mssim_buff
   if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
 }
 // FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
-template <bool FETCH>
+// PROFILE: the handle has a robot profile R: its static rule decides (the reward's norm stays over qvel[:n_static_dofs] for every robot)
+template <bool FETCH, bool PROFILE>
 __global__ __launch_bounds__(256) void k_task_poke(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_poke_task T, const int* __restrict__ pairs, int npairs,
-                                                    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics) {
+                                                    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics,
+                                                    mssim_task_robot R) {
   int e;
   if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
   else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  if constexpr (PROFILE) T.static_thresh = profile_static_thresh(R, B.art_qvel + (size_t)e * M.n_dof);
   task_poke_env(M, S, B, T, pairs, npairs, obs, reward, flags, metrics, e);
 }
 
@@ -1103,12 +1127,14 @@ MS_DEV void task_place_env(const DevModel& M, const DevState& S, const mssim_buf
   if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
 }
 // FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
-template <bool FETCH>
+// PROFILE: the handle has a robot profile R: its static rule gives the robot_static term of the on-bin tier
+template <bool FETCH, bool PROFILE>
 __global__ __launch_bounds__(256) void k_task_place(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_place_task T, const int* __restrict__ pairs, int npairs,
-                                                     float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags) {
+                                                     float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, mssim_task_robot R) {
   int e;
   if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
   else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  if constexpr (PROFILE) T.robot_static_thresh = profile_static_thresh(R, B.art_qvel + (size_t)e * M.n_dof);
   task_place_env(M, S, B, T, pairs, npairs, obs, reward, flags, e);
 }
 
@@ -1370,6 +1396,7 @@ struct mssim_sim {
   // finger <-> object candidate pairs of the task epilogue that asked last, and the (object, finger, finger) rows they are for
   int* d_finger_pairs = nullptr; int n_finger_pairs = 0; int finger_pair_rows[3] = {-1, -1, -1};
   long long n_tail_steps = 0;  // control steps that ran with the task epilogue at the kernel's tail (mssim_tail_step_count)
+  mssim_task_robot task_robot = {};  // mssim_set_task_robot; n_ranges == 0: the rules of the task structs (the Panda's)
   std::vector<int*> queries;
   std::vector<int> query_n;
   std::vector<int> query_kind;
@@ -1955,7 +1982,7 @@ template <class Task, size_t NROWS, class Standalone>
 static int task_outputs(mssim_handle h, const TaskCall& c, Task TailTask::*slot, const Task* task, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
   if (int rc = task_refusals(h, c, rows)) return rc;
   const Owed& o = h->owed;
-  if (h->tail_fn[c.id] && o.action && o.fetch && o.nsub > 0 && st == o.stream && h->ee.link < 0 && h->ik.link < 0) {
+  if (h->tail_fn[c.id] && o.action && o.fetch && o.nsub > 0 && st == o.stream && h->ee.link < 0 && h->ik.link < 0 && h->task_robot.n_ranges == 0) {
     DevState S = state_with_action(h, o.action, o.adim);
     S.tail_task.*slot = *task;
     S.tail_pairs = c.pair_rows ? h->d_finger_pairs : nullptr; S.tail_npairs = c.pair_rows ? h->n_finger_pairs : 0;
@@ -1981,8 +2008,9 @@ int mssim_task_pick_outputs(mssim_handle h, const mssim_pick_task* task, float* 
   const int pair_rows[] = {task->obj_row, task->finger1_row, task->finger2_row};
   const TaskCall call{mssim_dispatch::kPick, "pick", /*refused=*/nullptr, pair_rows, obs, reward, flags, /*extra=*/nullptr};
   return task_outputs(h, call, &TailTask::pick, task, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
-    hipLaunchKernelGGL(k_task_pick<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
-                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags);
+    const auto k = h->task_robot.n_ranges > 0 ? k_task_pick<decltype(fetch)::value, true> : k_task_pick<decltype(fetch)::value, false>;
+    hipLaunchKernelGGL(k, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, h->task_robot);
   });
 }
 
@@ -2059,8 +2087,9 @@ int mssim_task_poke_outputs(mssim_handle h, const mssim_poke_task* task, float* 
                       obs, reward, flags, metrics};
   return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
     // launch shapes as mssim_task_pick_outputs
-    hipLaunchKernelGGL(k_task_poke<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
-                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, metrics);
+    const auto k = h->task_robot.n_ranges > 0 ? k_task_poke<decltype(fetch)::value, true> : k_task_poke<decltype(fetch)::value, false>;
+    hipLaunchKernelGGL(k, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, metrics, h->task_robot);
   });
 }
 
@@ -2082,8 +2111,9 @@ int mssim_task_place_outputs(mssim_handle h, const mssim_place_task* task, float
                       obs, reward, flags, /*extra=*/nullptr};
   return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
     // launch shapes as mssim_task_pick_outputs
-    hipLaunchKernelGGL(k_task_place<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
-                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags);
+    const auto k = h->task_robot.n_ranges > 0 ? k_task_place<decltype(fetch)::value, true> : k_task_place<decltype(fetch)::value, false>;
+    hipLaunchKernelGGL(k, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, h->task_robot);
   });
 }
 
@@ -2099,6 +2129,18 @@ int mssim_task_pulltool_outputs(mssim_handle h, const mssim_pulltool_task* task,
 }
 
 int64_t mssim_tail_step_count(mssim_handle h) { return h ? h->n_tail_steps : -1; }
+
+int mssim_set_task_robot(mssim_handle h, const mssim_task_robot* robot) {
+  if (!h) return 1;
+  if (!robot || robot->n_ranges == 0) { h->task_robot = mssim_task_robot{}; return 0; }
+  const int n = h->M.n_dof;
+  bool ok = robot->n_ranges >= 1 && robot->n_ranges <= 2 && robot->pick_norm_dofs >= 0 && robot->pick_norm_dofs <= n;
+  for (int r = 0; ok && r < robot->n_ranges; r++)
+    ok = robot->first[r] >= 0 && robot->count[r] >= 0 && robot->first[r] <= n && robot->count[r] <= n - robot->first[r] && robot->thresh[r] == robot->thresh[r];
+  if (!ok) { h->err = "set_task_robot: up to two joint ranges within [0, n_dof) with a threshold each, and a norm over at most n_dof joints"; return 3; }
+  h->task_robot = *robot;
+  return 0;
+}
 
 static int make_query(mssim_handle h, const int32_t* data, int count_ints, int nq, int kind, int32_t* qid) {
   HIPCHK(h, hipSetDevice(h->device));

@@ -101,22 +101,24 @@ class LiftPegUprightEnv(BaseEnv):
             getattr(cls, m) is getattr(LiftPegUprightEnv, m)
             for m in ("evaluate", "_get_obs_extra", "compute_dense_reward", "compute_normalized_dense_reward", "_get_obs_agent", "get_obs", "get_info", "get_reward")
         )
-        from maniskill_amd.agents.robots.panda import Panda
+        from maniskill_amd.envs.utils.task_robot import fused_robot_ok
 
-        return (same and self.robot_uids == "panda" and type(self.agent).is_grasping is Panda.is_grasping and self._obs_mode == "state"
+        return (same and fused_robot_ok(self, ("panda",)) and self._obs_mode == "state"
                 and self._reward_mode in ("dense", "normalized_dense") and len(self.agent.controller.get_state()) == 0)
 
     def _fused_step_outputs(self, action, advance: bool = True):
         if not self._fused_ok():
             return None
         from maniskill_amd import native
+        from maniskill_amd.envs.utils.task_robot import fused_robot_rows
 
         px = self.scene.px
         st = getattr(self, "_fused_state", None)
         if st is None or st["px"] is not px:
+            finger1_row, finger2_row = fused_robot_rows(self)
             task = native.LiftPegTask(
                 tcp_row=self.agent.tcp._body_row, peg_row=self.peg._body_row,
-                finger1_row=self.agent.finger1_link._body_row, finger2_row=self.agent.finger2_link._body_row,
+                finger1_row=finger1_row, finger2_row=finger2_row,
                 peg_half_length=self.peg_half_length, upright_thresh=0.08, height_thresh=0.005, min_force=0.5, max_angle_deg=85.0,
                 reward_scale=1.0 / 3.0 if self._reward_mode == "normalized_dense" else 1.0,
             )

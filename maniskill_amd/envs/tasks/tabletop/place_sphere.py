@@ -144,10 +144,10 @@ class PlaceSphereEnv(BaseEnv):
             for m in ("evaluate", "_get_obs_extra", "compute_dense_reward", "compute_normalized_dense_reward", "_gripper_width", "_get_obs_agent", "get_obs",
                       "get_info", "get_reward")
         )
-        from maniskill_amd.agents.robots.panda import Panda
+        from maniskill_amd.envs.utils.task_robot import fused_robot_ok
         from maniskill_amd.utils.structs.actor import Actor
 
-        return (same and self.robot_uids == "panda" and type(self.agent).is_grasping is Panda.is_grasping and type(self.agent).is_static is Panda.is_static
+        return (same and fused_robot_ok(self, ("panda",), needs_static=True)
                 and type(self.obj).is_static is Actor.is_static and self._obs_mode == "state" and self._reward_mode in ("dense", "normalized_dense")
                 and len(self.agent.controller.get_state()) == 0)
 
@@ -155,13 +155,15 @@ class PlaceSphereEnv(BaseEnv):
         if not self._fused_ok():
             return None
         from maniskill_amd import native
+        from maniskill_amd.envs.utils.task_robot import apply_robot_profile, fused_robot_rows
 
         px = self.scene.px
         st = getattr(self, "_fused_state", None)
         if st is None or st["px"] is not px:
+            finger1_row, finger2_row = fused_robot_rows(self)
             task = native.PlaceTask(
                 tcp_row=self.agent.tcp._body_row, obj_row=self.obj._body_row, bin_row=self.bin._body_row,
-                finger1_row=self.agent.finger1_link._body_row, finger2_row=self.agent.finger2_link._body_row,
+                finger1_row=finger1_row, finger2_row=finger2_row,
                 n_static_dofs=self.agent.robot.max_dof - 2, radius=self.radius, bin_base_half=self.block_half_size[0], on_bin_tol=0.005,
                 static_lin_thresh=1e-2, static_ang_thresh=0.5, robot_static_thresh=0.2, gripper_width=float(self._gripper_width()), min_force=0.5,
                 max_angle_deg=85.0, reward_scale=1.0 / 13.0 if self._reward_mode == "normalized_dense" else 1.0,
@@ -172,6 +174,7 @@ class PlaceSphereEnv(BaseEnv):
         reward = torch.empty((N,), dtype=torch.float32, device=self.device)
         flags = torch.empty((N, 4), dtype=torch.uint8, device=self.device)
         es = self._fused_bind_counters(st["task"], advance)
+        apply_robot_profile(self, 0.2)
         px.task_place_outputs(st["task"], obs, reward, flags)
         fb = flags.view(torch.bool)
         info = dict(elapsed_steps=es, is_obj_grasped=fb[:, 1], is_obj_on_bin=fb[:, 2], is_obj_static=fb[:, 3], success=fb[:, 0])

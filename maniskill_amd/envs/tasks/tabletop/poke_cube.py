@@ -163,22 +163,24 @@ class PokeCubeEnv(BaseEnv):
             for m in ("evaluate", "_euler_z", "peg_head_pos", "peg_head_pose", "_get_obs_extra", "compute_dense_reward", "compute_normalized_dense_reward",
                       "_get_obs_agent", "get_obs", "get_info", "get_reward")
         )
-        from maniskill_amd.agents.robots.panda import Panda
+        from maniskill_amd.envs.utils.task_robot import fused_robot_ok
 
-        return (same and self.robot_uids == "panda" and type(self.agent).is_grasping is Panda.is_grasping and type(self.agent).is_static is Panda.is_static
+        return (same and fused_robot_ok(self, ("panda",), needs_static=True)
                 and self._obs_mode == "state" and self._reward_mode in ("dense", "normalized_dense") and len(self.agent.controller.get_state()) == 0)
 
     def _fused_step_outputs(self, action, advance: bool = True):
         if not self._fused_ok():
             return None
         from maniskill_amd import native
+        from maniskill_amd.envs.utils.task_robot import apply_robot_profile, fused_robot_rows
 
         px = self.scene.px
         st = getattr(self, "_fused_state", None)
         if st is None or st["px"] is not px:
+            finger1_row, finger2_row = fused_robot_rows(self)
             task = native.PokeTask(
                 tcp_row=self.agent.tcp._body_row, peg_row=self.peg._body_row, cube_row=self.cube._body_row, goal_row=self.goal_region._body_row,
-                finger1_row=self.agent.finger1_link._body_row, finger2_row=self.agent.finger2_link._body_row,
+                finger1_row=finger1_row, finger2_row=finger2_row,
                 n_static_dofs=self.agent.robot.max_dof - 2, peg_half_length=self.peg_half_length, cube_half_size=self.cube_half_size,
                 goal_radius=self.goal_radius, align_thresh=0.05, reach_thresh=0.01, static_thresh=0.2, min_force=0.5,
                 max_angle_deg=85.0, reward_scale=0.1 if self._reward_mode == "normalized_dense" else 1.0,
@@ -190,6 +192,7 @@ class PokeCubeEnv(BaseEnv):
         flags = torch.empty((N, 4), dtype=torch.uint8, device=self.device)
         metrics = torch.empty((N, 2), dtype=torch.float32, device=self.device)
         es = self._fused_bind_counters(st["task"], advance)
+        apply_robot_profile(self, 0.2)
         px.task_poke_outputs(st["task"], obs, reward, flags, metrics)
         fb = flags.view(torch.bool)
         info = dict(elapsed_steps=es, success=fb[:, 0], is_cube_placed=fb[:, 1], is_peg_cube_fit=fb[:, 2], is_peg_grasped=fb[:, 3],

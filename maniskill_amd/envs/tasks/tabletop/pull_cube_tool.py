@@ -155,10 +155,10 @@ class PullCubeToolEnv(BaseEnv):
             getattr(cls, m) is getattr(PullCubeToolEnv, m)
             for m in ("evaluate", "_get_obs_extra", "compute_dense_reward", "compute_normalized_dense_reward", "_get_obs_agent", "get_obs", "get_info", "get_reward")
         )
-        from maniskill_amd.agents.robots.panda import Panda
+        from maniskill_amd.envs.utils.task_robot import fused_robot_ok
 
         # (panda_wristcam: the Panda's kinematics and fingers on another mount; the camera adds nothing to the state obs)
-        return (same and self.robot_uids in ("panda", "panda_wristcam") and type(self.agent).is_grasping is Panda.is_grasping and self._obs_mode == "state"
+        return (same and fused_robot_ok(self, ("panda", "panda_wristcam")) and self._obs_mode == "state"
                 and self._reward_mode in ("dense", "normalized_dense") and len(self.agent.controller.get_state()) == 0)
 
     def _fused_step_outputs(self, action, advance: bool = True):
@@ -169,14 +169,16 @@ class PullCubeToolEnv(BaseEnv):
         if not self._fused_ok():
             return None
         from maniskill_amd import native
+        from maniskill_amd.envs.utils.task_robot import fused_robot_rows
 
         px = self.scene.px
         st = getattr(self, "_fused_state", None)
         if st is None or st["px"] is not px:
+            finger1_row, finger2_row = fused_robot_rows(self)
             task = native.PullToolTask(
                 tcp_row=self.agent.tcp._body_row, cube_row=self.cube._body_row, tool_row=self.l_shape_tool._body_row,
                 base_row=self.agent.robot.get_links()[0]._body_row,
-                finger1_row=self.agent.finger1_link._body_row, finger2_row=self.agent.finger2_link._body_row,
+                finger1_row=finger1_row, finger2_row=finger2_row,
                 cube_half_size=self.cube_half_size, hook_length=self.hook_length, arm_reach=self.arm_reach, cube_size=self.cube_size, pulled_close_dist=0.6,
                 min_force=0.5, max_angle_deg=20.0, reward_scale=0.2 if self._reward_mode == "normalized_dense" else 1.0,
             )

@@ -130,13 +130,12 @@ class StackCubeEnv(BaseEnv):
             for m in ("evaluate", "_get_obs_extra", "compute_dense_reward", "compute_normalized_dense_reward", "_gripper_width", "_get_obs_agent", "get_obs",
                       "get_info", "get_reward")
         )
-        from maniskill_amd.agents.robots.panda import Panda
+        from maniskill_amd.envs.utils.task_robot import fused_robot_ok
 
         # (panda_wristcam: the Panda's kinematics and fingers on another mount; the camera adds nothing to the state obs)
         ok = (
             same
-            and self.robot_uids in ("panda", "panda_wristcam")
-            and type(self.agent).is_grasping is Panda.is_grasping
+            and fused_robot_ok(self, ("panda", "panda_wristcam"))
             and self._obs_mode == "state"
             and self._reward_mode in ("dense", "normalized_dense")
             and len(self.agent.controller.get_state()) == 0
@@ -147,14 +146,16 @@ class StackCubeEnv(BaseEnv):
         if not self._fused_ok():
             return None
         from maniskill_amd import native
+        from maniskill_amd.envs.utils.task_robot import fused_robot_rows
 
         px = self.scene.px
         st = getattr(self, "_fused_state", None)
         if st is None or st["px"] is not px:
             hs = self.cube_half_size.float()
+            finger1_row, finger2_row = fused_robot_rows(self)
             task = native.StackTask(
                 tcp_row=self.agent.tcp._body_row, cubeA_row=self.cubeA._body_row, cubeB_row=self.cubeB._body_row,
-                finger1_row=self.agent.finger1_link._body_row, finger2_row=self.agent.finger2_link._body_row,
+                finger1_row=finger1_row, finger2_row=finger2_row,
                 # (the thresholds as evaluate() computes them in float32, so that the flags agree bit for bit)
                 cube_half_size=float(hs[2]), on_xy_thresh=float(torch.linalg.norm(hs[:2]) + 0.005), on_z_thresh=0.005,
                 gripper_width=float(self._gripper_width()), static_lin_thresh=1e-2, static_ang_thresh=0.5, min_force=0.5, max_angle_deg=85.0,

@@ -215,6 +215,12 @@ class PullToolTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class TaskRobot(C.Structure):
+    """mssim_task_robot of include/mssim_hip_tasks.h (HIP library only): the robot-dependent rules of the task epilogues"""
+    _fields_ = [("n_ranges", C.c_int32), ("first", C.c_int32 * 2), ("count", C.c_int32 * 2), ("thresh", C.c_float * 2),
+                ("signed_compare", C.c_int32), ("pick_norm_dofs", C.c_int32)]
+
+
 class EeIkMap(C.Structure):
     """mssim_ee_ik_map of include/mssim_hip_tasks.h (HIP library only)"""
     _fields_ = [("link_index", C.c_int32), ("column0", C.c_int32), ("rows", C.c_int32), ("mode", C.c_int32),
@@ -329,6 +335,7 @@ class NativeLib:
             ("task_place_outputs", C.c_int, [H, C.POINTER(PlaceTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_pulltool_outputs", C.c_int, [H, C.POINTER(PullToolTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
+            ("set_task_robot", C.c_int, [H, C.POINTER(TaskRobot)]),
             ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
             ("ee_ik_solve", C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("raycast_create", C.c_int, [H, C.POINTER(RaycastScene), C.POINTER(CameraDesc), C.c_int32, _I32P]),
@@ -529,6 +536,12 @@ class NativeSim:
         if self.lib.tail_step_count is None:
             raise NativeError(f"{self.lib.path} has no tail_step_count (an extra of the HIP library, include/mssim_hip_tasks.h)")
         return int(self.lib.tail_step_count(self.h))
+
+    def set_task_robot(self, robot: Optional["TaskRobot"]):
+        """robot profile of the task epilogues (HIP library only); None removes it"""
+        if self.lib.set_task_robot is None:
+            raise NativeError(f"{self.lib.path} has no set_task_robot (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.set_task_robot(self.h, None if robot is None else C.byref(robot)), "set_task_robot")
 
     def set_ee_ik_map(self, ik: "EeIkMap", target_pose_ptr):
         """iterative-IK block of the action map (HIP library only); `ik.link_index < 0` removes it"""

@@ -368,6 +368,24 @@ class MssimSystem:
         else:
             self._sim.step_action(action.data_ptr(), action.shape[1], n_substeps, self._stream())
 
+    task_robot = None  # the profile set last (a tuple of ranges, signed, norm dofs), None: the rules of the task structs
+
+    def set_task_robot(self, ranges=None, signed_compare: bool = False, pick_norm_dofs: int = 0):
+        """robot profile of the task epilogues (include/mssim_hip_tasks.h `mssim_set_task_robot`; HIP library only):
+        `ranges` = up to two `(first joint, joint count, threshold)` of the robot's is_static, compared signed or by
+        absolute value; `pick_norm_dofs` = leading joints of PickCube's reward norm. `ranges=None` removes the profile.
+        While one is set every epilogue is a launch of its own."""
+        if not ranges:
+            if self._sim.lib.set_task_robot is not None:  # (a library without profiles has none to remove)
+                self._sim.set_task_robot(None)
+            self.task_robot = None
+            return
+        r = native.TaskRobot(n_ranges=len(ranges), signed_compare=int(bool(signed_compare)), pick_norm_dofs=int(pick_norm_dofs))
+        for i, (first, count, thresh) in enumerate(ranges):
+            r.first[i], r.count[i], r.thresh[i] = int(first), int(count), float(thresh)
+        self._sim.set_task_robot(r)
+        self.task_robot = (tuple((int(a), int(b), float(c)) for a, b, c in ranges), bool(signed_compare), int(pick_norm_dofs))
+
     def task_peg_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor, head: torch.Tensor):
         self._sim.task_peg_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), head.data_ptr(), self._stream())
 

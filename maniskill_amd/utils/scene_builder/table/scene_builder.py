@@ -1,16 +1,19 @@
 """Table-top scene (counterpart of mani_skill/utils/scene_builder/table/scene_builder.py:20-134):
 kinematic table box whose top face is z = 0, ground plane at -table_height, robot initial qpos =
-rest keyframe + N(0, robot_init_qpos_noise) drawn from the numpy episode RNG."""
+rest keyframe + N(0, robot_init_qpos_noise) drawn from the numpy episode RNG. The Fetch stands on the ground behind
+the table, at a fixed qpos without noise (scene_builder.py:171-196 of the reference)."""
 import numpy as np
 import sapien
 import torch
 from transforms3d.euler import euler2quat
 
+from maniskill_amd.agents.robots.fetch import FETCH_WHEELS_COLLISION_BIT
 from maniskill_amd.utils.building.ground import build_ground
 from maniskill_amd.utils.scene_builder.scene_builder import SceneBuilder
 from maniskill_amd.utils.structs.pose import Pose
 
 TABLE_HEIGHT = 0.9196429
+FETCH_QPOS = np.array([0, 0, 0, 0.386, 0, 0, 0, -np.pi / 4, 0, np.pi / 4, 0, np.pi / 3, 0, 0.015, 0.015])
 
 
 class TableSceneBuilder(SceneBuilder):
@@ -24,6 +27,10 @@ class TableSceneBuilder(SceneBuilder):
         self.table_width = 2.418
         self.table_height = TABLE_HEIGHT
         self.ground = build_ground(self.scene, floor_width=100, altitude=-self.table_height)
+        if self.env.robot_uids == "fetch":
+            # (the reference sets the bit at every initialize; the collision pairs here are compiled once, from the
+            # bits the shapes carry when the scene is built, as in Empty-v1)
+            self.ground.set_collision_group_bit(group=2, bit_idx=FETCH_WHEELS_COLLISION_BIT, bit=1)
         self.table = table
         self.scene_objects = [self.table, self.ground]
 
@@ -40,7 +47,8 @@ class TableSceneBuilder(SceneBuilder):
         dev = self.env.device
         if cache.get("device") != dev:
             cache.update(device=dev, table=Pose.create(sapien.Pose(p=[-0.12, 0, -TABLE_HEIGHT], q=euler2quat(0, 0, np.pi / 2)), device=dev),
-                         root=Pose.create(sapien.Pose([-0.615, 0, 0]), device=dev))
+                         root=Pose.create(sapien.Pose([-0.615, 0, 0]), device=dev),
+                         fetch_root=Pose.create(sapien.Pose([-1.05, 0, -TABLE_HEIGHT]), device=dev))
         self.table.set_pose(cache["table"])
         uid = self.env.robot_uids
         if uid == "panda":
@@ -49,6 +57,10 @@ class TableSceneBuilder(SceneBuilder):
             qpos = np.array([0.0, np.pi / 8, 0, -np.pi * 5 / 8, 0, np.pi * 3 / 4, -np.pi / 4, 0.04, 0.04])
         elif uid == "panda_stick":  # (no fingers: no gripper overwrite below)
             qpos = np.array([0.0, np.pi / 8, 0, -np.pi * 5 / 8, 0, np.pi * 3 / 4, np.pi / 4])
+        elif uid == "fetch":  # (no noise for this robot)
+            self.env.agent.reset(np.tile(FETCH_QPOS, (len(env_idx), 1)))
+            self.env.agent.robot.set_pose(cache["fetch_root"])
+            return
         elif uid in (None, "none"):
             return
         else:

@@ -70,9 +70,16 @@ for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("Pe
                  # the Fetch's end-effector modes: base and torso are on the gripper's path and held by the two blocks
                  # (`fetch_ee` selects these four rows alone; MS_FUSED=0: the torch solver)
                  *((("Empty-v1", 1024), dict(robot_uids="fetch", control_mode=m))
-                   for m in ("pd_ee_delta_pos", "pd_ee_delta_pose", "pd_ee_target_delta_pos", "pd_ee_target_delta_pose"))):
+                   for m in ("pd_ee_delta_pos", "pd_ee_delta_pose", "pd_ee_target_delta_pos", "pd_ee_target_delta_pose")),
+                 # table-top tasks with the Fetch: the two-row 15-dof plain control step + the epilogue under the Fetch's robot
+                 # profile as a launch of its own (`fetch_tabletop` selects these two rows alone; MS_FUSED=0: the torch epilogue)
+                 (("PickCube-v1", 4096), dict(robot_uids="fetch")), (("PullCubeTool-v1", 4096), dict(robot_uids="fetch"))):
     fetch_ee = kw.get("robot_uids") == "fetch" and "control_mode" in kw
-    if "fetch_ee" in only and not fetch_ee:
+    fetch_tabletop = kw.get("robot_uids") == "fetch" and args[0] != "Empty-v1"
+    if ("fetch_ee" in only and not fetch_ee) or (fetch_tabletop and only and "fetch_tabletop" not in only):
+        continue
+    if fetch_tabletop and "fetch_tabletop" in only:
+        run(*args, **kw)
         continue
     if not only or args[0] in only or kw.get("control_mode") in only or ("substeps4" in only and "sim_config" in kw) or ("fetch_ee" in only and fetch_ee):
         run(*args, **kw)

@@ -19,6 +19,8 @@ MS_ROBOT=fetch run Empty-v1 1024 2000 pd_ee_delta_pos
 MS_ROBOT=fetch run Empty-v1 1024 2000 pd_ee_delta_pose
 MS_ROBOT=fetch run Empty-v1 1024 2000 pd_ee_target_delta_pos
 MS_ROBOT=fetch run Empty-v1 1024 2000 pd_ee_target_delta_pose
+MS_ROBOT=fetch run PickCube-v1 4096 2000 pd_joint_delta_pos
+MS_ROBOT=fetch run PullCubeTool-v1 4096 2000 pd_joint_delta_pos
 run SceneManipulation-v1 1024 3000 pd_joint_delta_pos
 MS_SCENE_BUILDER=SyntheticRoomsCrowded run SceneManipulation-v1 1024 2000 pd_joint_delta_pos
 grep -c "soak ok" $O; grep -n "FAILED\|Error\|assert" $O | head
