@@ -244,6 +244,35 @@ typedef struct mssim_pulltool_task {
 
 int mssim_task_pulltool_outputs(mssim_handle h, const mssim_pulltool_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream);
 
+/* PlugCharger-style evaluate + state observation + (zero) dense reward in one launch (envs/tasks/tabletop/plug_charger.py).
+ * The goal is not a body row: `goal_pose` is the env's stored [N][7] tensor (p, q wxyz), written at reset; a receptacle
+ * moved afterwards leaves it where it was. No grasp and no robot rule is read: no contact pairs, no robot profile. Like the
+ * six tasks above, this one never runs at the control-step kernel's tail (the one-row plain step, then this launch).
+ * obs [N][2*n_dof+28] f32 (qpos, qvel, tcp_pose7, charger_pose7, receptacle_pose7, goal_pose7), reward [N] f32 = 0 times
+ * reward_scale (the task definition's dense reward is zero), flags [N][1] u8 = success,
+ * metrics [N][2] f32 = obj_to_goal_dist, obj_to_goal_angle; required.
+ *   dist = |goal.p - charger.p|
+ *   r = conj(goal.q) * charger.q (Hamilton product, no normalisation), negated where r.w < 0 (quaternion_multiply's
+ *   standardisation); angle = 2 atan2(|r.xyz|, r.w), in [0, pi] since r.w >= 0: the task definition's min(a, 2 pi - a) is
+ *   then inert and is not applied. (The task definition reaches the same angle as |r.xyz / k|, k = sin(a / 2) / a.)
+ *   success = dist <= dist_thresh and angle <= angle_thresh
+ * A NaN in the charger's or the goal's position gives a NaN dist, one in either quaternion a NaN angle; every comparison
+ * with a NaN is false, so success is 0 for that env, and for that env alone. The observation copies NaNs as they are. */
+typedef struct mssim_plug_task {
+  int32_t tcp_row, charger_row, receptacle_row; /* rigid_body_data body rows */
+  const float* goal_pose;     /* device [N][7] p, q(wxyz): read at every call, kept by the caller; required */
+  float dist_thresh;          /* 5e-3 m  */
+  float angle_thresh;         /* 0.2 rad */
+  float reward_scale;         /* 1 (dense and normalized_dense: the reward is zero either way) */
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;     /* optional device [N]: new elapsed_steps >= time_limit */
+  int32_t time_limit;
+  uint8_t* terminated_out;    /* optional device [N]: a copy of success */
+} mssim_plug_task;
+
+int mssim_task_plug_outputs(mssim_handle h, const mssim_plug_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream);
+
 /* The robot-dependent rules of the task epilogues, stored on the handle: what "the robot is static" means and how many
  * joints the velocity norm of PickCube's static reward covers. With no profile set (or after a NULL / n_ranges == 0 call)
  * every epilogue applies the Panda's rules from its own task struct, as before: static = max |qvel[:n_static_dofs]| <=

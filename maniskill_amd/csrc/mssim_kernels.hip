@@ -1199,6 +1199,57 @@ __global__ __launch_bounds__(256) void k_task_pulltool(DevModel M, DevState S, m
   task_pulltool_env(M, S, B, T, pairs, npairs, obs, reward, flags, metrics, e);
 }
 
+// PlugCharger evaluate / obs / reward (plug_charger.py evaluate, _get_obs_extra; the dense reward is zero). The goal comes
+// from the env's stored tensor T.goal_pose [N][7], not from a body row. The angle is taken from the relative quaternion
+// r = conj(goal.q) * charger.q directly, 2 atan2(|r.xyz|, r.w) after the sign flip to r.w >= 0 that quaternion_multiply
+// makes: the torch path's |r.xyz / (sin(a / 2) / a)| is the same number, and its min(a, 2 pi - a) cannot bite for a <= pi.
+// A NaN pose gives NaN metrics and, every comparison with a NaN being false, success = 0.
+// One lane per env; never at the control-step kernel's tail.
+MS_DEV void task_plug_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_plug_task& T,
+                          float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics, int e) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  float* o = obs + (size_t)e * (2 * n + 28);
+  auto rowp = [&](int row) { return B.rigid_body_data + 13 * ((size_t)row * N + e); };
+  for (int j = 0; j < n; j++) {
+    o[j] = B.art_qpos[(size_t)e * n + j];
+    o[n + j] = B.art_qvel[(size_t)e * n + j];
+  }
+  const float* tcp = rowp(T.tcp_row);
+  const float* ch = rowp(T.charger_row);
+  const float* rc = rowp(T.receptacle_row);
+  const float* gl = T.goal_pose + 7 * (size_t)e;
+  int k = 2 * n;
+  for (int i = 0; i < 7; i++) o[k++] = tcp[i];
+  for (int i = 0; i < 7; i++) o[k++] = ch[i];
+  for (int i = 0; i < 7; i++) o[k++] = rc[i];
+  for (int i = 0; i < 7; i++) o[k++] = gl[i];
+  // evaluate
+  const float dist = norm(f3{gl[0], gl[1], gl[2]} - f3{ch[0], ch[1], ch[2]});
+  const float aw = gl[3];
+  const f3 av = f3{-gl[4], -gl[5], -gl[6]}, bv = f3{ch[4], ch[5], ch[6]};
+  const float bw = ch[3];
+  float rw = aw * bw - dot(av, bv);
+  f3 rv = bv * aw + av * bw + cross(av, bv);
+  if (rw < 0.f) { rw = -rw; rv = -rv; }
+  const float angle = 2.f * atan2f(norm(rv), rw);
+  const bool success = dist <= T.dist_thresh && angle <= T.angle_thresh;
+  reward[e] = 0.f * T.reward_scale;
+  flags[e] = success;
+  metrics[2 * (size_t)e] = dist; metrics[2 * (size_t)e + 1] = angle;
+  if (T.terminated_out) T.terminated_out[e] = success;
+  if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+}
+// FETCH: the launch first performs mssim_fetch(what) for its envs (fetch_in_block; 256 threads per block)
+template <bool FETCH>
+__global__ __launch_bounds__(256) void k_task_plug(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_plug_task T,
+                                                    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, float* __restrict__ metrics) {
+  int e;
+  if (FETCH) { e = fetch_in_block(M, S, B, what); if (e < 0) return; }
+  else { e = xcd_chunk(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; if (e >= S.N) return; }
+  task_plug_env(M, S, B, T, obs, reward, flags, metrics, e);
+}
+
 // PushT pseudo-render (push_t.py pseudo_render_intersection): every template pixel (i, j) of the block's T, at its uv
 // grid centre (U[j], V[i], 1), is mapped by world_to_goal @ tee_to_world, divided by the third row, scaled to pixel
 // indices and truncated toward zero (.long()); an index outside [0, 64) sends the pixel to (0, 0). Index pair (x, y)
@@ -1940,7 +1991,7 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
   return 0;
 }
 
-// A task epilogue, the one sequence behind the eleven mssim_task_*_outputs. Refusals come first and leave what is owed owed.
+// A task epilogue, the one sequence behind the twelve mssim_task_*_outputs. Refusals come first and leave what is owed owed.
 // An owed step_action + an owed fetch + the epilogue = ONE launch of the control-step kernel, where mssim_create found an
 // instance with the task's tail for the model (h->tail_fn). Otherwise what is owed is performed and the epilogue is a launch
 // of its own: `standalone(std::true_type, what, st)` launches k_task_*<true>, which first performs the owed copy-out `what`,
@@ -1967,7 +2018,7 @@ static int task_refusals(mssim_handle h, const TaskCall& c, const int (&rows)[NR
   return 0;
 }
 // The tail-less path, for a task without a member in the tail_task union (RollBall, PullCube, PokeCube, LiftPegUpright, PlaceSphere,
-// PullCubeTool: h->tail_fn[c.id] is null for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
+// PullCubeTool, PlugCharger: h->tail_fn[c.id] is null for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
 template <size_t NROWS, class Standalone>
 static int task_outputs(mssim_handle h, const TaskCall& c, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
   if (int rc = task_refusals(h, c, rows)) return rc;
@@ -2125,6 +2176,18 @@ int mssim_task_pulltool_outputs(mssim_handle h, const mssim_pulltool_task* task,
   return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
     hipLaunchKernelGGL(k_task_pulltool<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
                        h->M, h->S, h->buf, what, *task, h->d_finger_pairs, h->n_finger_pairs, obs, reward, flags, metrics);
+  });
+}
+
+int mssim_task_plug_outputs(mssim_handle h, const mssim_plug_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream) {
+  const int rows[] = {task->tcp_row, task->charger_row, task->receptacle_row};
+  const bool ok = task->goal_pose && metrics;
+  const TaskCall call{mssim_dispatch::kPlug, "plug", ok ? nullptr : "task_plug_outputs: needs the goal poses (device [N][7] f32) and the metrics output (device [N][2] f32)",
+                      /*pair_rows=*/nullptr, obs, reward, flags, metrics};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    // launch shapes as mssim_task_place_outputs
+    hipLaunchKernelGGL(k_task_plug<decltype(fetch)::value>, env_grid(h->N, 64), dim3(fetch ? 256 : 64), 0, st,
+                       h->M, h->S, h->buf, what, *task, obs, reward, flags, metrics);
   });
 }
 

@@ -215,6 +215,13 @@ class PullToolTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class PlugTask(C.Structure):
+    """mssim_plug_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("charger_row", C.c_int32), ("receptacle_row", C.c_int32), ("goal_pose", C.c_void_p),
+                ("dist_thresh", C.c_float), ("angle_thresh", C.c_float), ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
 class TaskRobot(C.Structure):
     """mssim_task_robot of include/mssim_hip_tasks.h (HIP library only): the robot-dependent rules of the task epilogues"""
     _fields_ = [("n_ranges", C.c_int32), ("first", C.c_int32 * 2), ("count", C.c_int32 * 2), ("thresh", C.c_float * 2),
@@ -334,6 +341,7 @@ class NativeLib:
             ("task_liftpeg_outputs", C.c_int, [H, C.POINTER(LiftPegTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_place_outputs", C.c_int, [H, C.POINTER(PlaceTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_pulltool_outputs", C.c_int, [H, C.POINTER(PullToolTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_plug_outputs", C.c_int, [H, C.POINTER(PlugTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
             ("set_task_robot", C.c_int, [H, C.POINTER(TaskRobot)]),
             ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
@@ -530,6 +538,11 @@ class NativeSim:
         if self.lib.task_pulltool_outputs is None:
             raise NativeError(f"{self.lib.path} has no task_pulltool_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.task_pulltool_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream), "task_pulltool_outputs")
+
+    def task_plug_outputs(self, task: "PlugTask", obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream=None):
+        if self.lib.task_plug_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_plug_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_plug_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream), "task_plug_outputs")
 
     def tail_step_count(self) -> int:
         """control steps that ran with the task epilogue at the control-step kernel's tail (HIP library only)"""

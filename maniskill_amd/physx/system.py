@@ -429,6 +429,11 @@ class MssimSystem:
         term, dense reward / 5, required (include/mssim_hip_tasks.h; HIP library only)"""
         self._sim.task_pulltool_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), None if metrics is None else metrics.data_ptr(), self._stream())
 
+    def task_plug_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor, metrics: Optional[torch.Tensor]):
+        """PlugCharger evaluate / obs / reward in one launch; metrics [N][2] f32 = obj_to_goal_dist, obj_to_goal_angle,
+        required; `task.goal_pose` points at the env's stored goal tensor (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_plug_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), None if metrics is None else metrics.data_ptr(), self._stream())
+
     # ------------------------------------------------------------------ ray-cast cameras (HIP only)
     def raycast_create(self, scene_arrays: dict, cameras: Sequence[dict]) -> int:
         """a ray-cast scene (`model.compile.raycast_scene`) with its cameras -> id for `raycast_render`

@@ -64,6 +64,9 @@ for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("Pe
                  (("PokeCube-v1", 4096), {}), (("LiftPegUpright-v1", 4096), {}),
                  # place-and-release against a five-box kinematic bin (one row), and panda_wristcam + cube + two-box tool (two rows)
                  (("PlaceSphere-v1", 4096), {}), (("PullCubeTool-v1", 4096), {}),
+                 # millimetre geometry: 1.5 mm pegs and a five-box receptacle (one row; the epilogue reads the env's stored goal).
+                 # `plug` selects this row alone and runs it twice in one process: native, then MS_FUSED=0 (the torch epilogue)
+                 (("PlugCharger-v1", 4096), {}),
                  (("PickCube-v1", 4096), dict(sim_config=dict(control_freq=25))),  # 4 substeps (SURVEY 8d reports 5 and 4)
                  # BASELINE config 5's robot and env count: the Fetch on an empty ground, and in synthetic triangle-mesh rooms
                  (("Empty-v1", 1024), dict(robot_uids="fetch")), (("SceneManipulation-v1", 1024), dict(build_config_idxs=[i % 5 for i in range(1024)])),
@@ -80,6 +83,13 @@ for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("Pe
         continue
     if fetch_tabletop and "fetch_tabletop" in only:
         run(*args, **kw)
+        continue
+    if "plug" in only and args[0] == "PlugCharger-v1":
+        before = os.environ.get("MS_FUSED")
+        for fused in ("1", "0"):  # (read when the env is made; each line's `fused` says which path ran)
+            os.environ["MS_FUSED"] = fused
+            run(*args, **kw)
+        os.environ.pop("MS_FUSED") if before is None else os.environ.__setitem__("MS_FUSED", before)
         continue
     if not only or args[0] in only or kw.get("control_mode") in only or ("substeps4" in only and "sim_config" in kw) or ("fetch_ee" in only and fetch_ee):
         run(*args, **kw)
