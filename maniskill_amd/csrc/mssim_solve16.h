@@ -1103,6 +1103,78 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
       WSYNC();
       if (__any(hit_over) && hit_over && live) atomicOr(&S.overflow[e], MSSIM_OVERFLOW_HITS);
       PH(23);
+      // sleeping free bodies (the patch pass, below): a "disturber" is an articulation link or a free body that is awake and
+      // not calm
+      auto free_of = [&](int slot1) { return (slot1 > S16_PT_FREE && slot1 <= S16_PT_FREE + S16_MAX_FREE) ? slot1 - 1 - S16_PT_FREE : -1; };
+      auto disturber = [&](int slot1) {
+        if (slot1 > S16_PT_LINK && slot1 <= S16_PT_FREE) return true;  // pose slots 1..16: articulation links
+        const int b = free_of(slot1);
+        return b >= 0 && fw_at(b) > 0.f && !fc_at(b);
+      };
+      // ---- doomed pairs: a sleeping free body none of whose hits has a disturber on its other side cannot wake in this
+      // substep, and the patch pass drops every manifold of a body that stays asleep (a sleeping cube on a kinematic table:
+      // the cull keeps that pair, the table may move). Such a body's box-box and plane hits carry nothing from one substep
+      // to the next, so they leave the hit list here, order preserved, and cost no manifold. Its generic-convex pairs stay
+      // (the stamps of their cache slots); mesh pairs are not in this list. The counts from before the removal still choose
+      // the box-box path (bb_lane, below), so no other pair changes its code path.
+      int nh_doomed = 0, nbl_doomed = 0;
+      {
+        bool any_asleep = false;
+#pragma unroll
+        for (int b = 0; b < S16_MAX_FREE; b++) any_asleep = any_asleep || (b < nf && fwake[b] <= 0.f);
+        if (__any(any_asleep && nh > 0)) {  // (wave-uniform)
+          int* const hit_ = reinterpret_cast<int*>(L + S16_NP_HIT);
+          auto b16 = [&](bool v) __attribute__((always_inline)) { return (unsigned)(__ballot(v) >> (16 * g)) & 0xFFFFu; };
+          // lane c looks after the hits c, c + 16, c + 32, c + 48
+          int hk[4];
+          unsigned zz[4];        // the hit's sleeping free bodies
+          bool light[4], bb_[4];  // a pair without cache state; a box-box pair
+          unsigned touch = 0u;   // bit b: sleeping free body b has a hit with a disturber
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            const int i = c + 16 * k;
+            hk[k] = 0; zz[k] = 0u; light[k] = false; bb_[k] = false;
+            if (i < nh) {
+              const int pk = hit_[i];
+              const unsigned pa = __float_as_uint(L[S16_NP_SHP + S16_SHP * ((pk >> 16) & 0xFF) + 14]), pb = __float_as_uint(L[S16_NP_SHP + S16_SHP * ((pk >> 24) & 0xFF) + 14]);
+              const int s1a = (int)((pa >> 10) & 31u), s1b = (int)((pb >> 10) & 31u);
+              const int ta = (int)(pa & 7u), tb = (int)(pb & 7u);
+              const int ba = free_of(s1a), bb = free_of(s1b);
+              if (ba >= 0 && fw_at(ba) <= 0.f) { zz[k] |= 1u << ba; if (disturber(s1b)) touch |= 1u << ba; }
+              if (bb >= 0 && fw_at(bb) <= 0.f) { zz[k] |= 1u << bb; if (disturber(s1a)) touch |= 1u << bb; }
+              hk[k] = pk;
+              bb_[k] = ta == SH_BOX && tb == SH_BOX;
+              light[k] = bb_[k] || (ta == SH_PLANE && tb != SH_TRIMESH);
+            }
+          }
+          touch |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)touch, 0x128, 0xF, 0xF, false);  // row_ror 8, 4, 2, 1: every lane of the group
+          touch |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)touch, 0x124, 0xF, 0xF, false);
+          touch |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)touch, 0x122, 0xF, 0xF, false);
+          touch |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)touch, 0x121, 0xF, 0xF, false);
+          bool doomed[4];
+          bool any_doomed = false;
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            doomed[k] = light[k] && (zz[k] & ~touch) != 0u;
+            any_doomed = any_doomed || doomed[k];
+          }
+          if (__any(any_doomed)) {  // (wave-uniform)
+            WSYNC();  // every lane holds its hits: the list is compacted in place
+            int w = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              const bool stay = c + 16 * k < nh && !doomed[k];
+              const unsigned m16 = b16(stay);
+              if (stay) hit_[w + __popc(m16 & ((1u << c) - 1u))] = hk[k];
+              w += __popc(m16);
+              nbl_doomed += __popc(b16(doomed[k] && bb_[k]));
+            }
+            nh_doomed = nh - w;
+            nh = w;
+            WSYNC();
+          }
+        }
+      }
       // ---- classification: generic convex pairs (MPR) and box-box pairs of this env (byte lists of hit indices)
       int nml = 0;  // MPR pairs of this env
       int nbl = 0;  // box-box pairs of this env
@@ -1150,12 +1222,20 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
         mcum[j + 1] = mcum[j] + __shfl(nml, GW * j);
         bcum[j + 1] = bcum[j] + __shfl(nbl, GW * j);
       }
-      const int T = cum[EPW], TM = mcum[EPW], TB = bcum[EPW];
+      const int T = cum[EPW], TM = mcum[EPW];
+      int T_all = T, TB = bcum[EPW];  // (with the doomed pairs: the counts that choose the box-box path)
+      if (nf > 0) {
+#pragma unroll
+        for (int j = 0; j < EPW; j++) {
+          T_all += __shfl(nh_doomed, GW * j);
+          TB += __shfl(nbl_doomed, GW * j);
+        }
+      }
       // Box-box pairs: with few of them in the wave (the usual case: cube on table, peg on table) one lane per pair
       // leaves the wave almost empty for ~3400 instructions, so the 4 groups take them round-robin, 16 lanes per
       // pair (stage C). Many of them (fingers on the table: 8 per env): one lane per pair (stage A), whose clip
       // scratch is this area -- only possible while all tasks of the wave fit one round.
-      const bool bb_lane = NR == 1 && TB > S16_MAX_BBC && T <= 64;  // wave-uniform (the clip scratch holds one column per lane of a 16-lane env)
+      const bool bb_lane = NR == 1 && TB > S16_MAX_BBC && T_all <= 64;  // wave-uniform (the clip scratch holds one column per lane of a 16-lane env)
       bool pool_over = false;
       WSYNC();
       PH_ADD(14, (TM + EPW - 1) / EPW);
@@ -1998,49 +2078,69 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
         int* const keep_ = reinterpret_cast<int*>(L + S16_NP_KEEP);
         int* const key_ = reinterpret_cast<int*>(L + S16_NP_KEY);
         const int* const hit_ = reinterpret_cast<const int*>(L + S16_NP_HIT);
-        for (int i = c; i < nh; i += 16) {
-          const int pk = hit_[i];
-          const unsigned pa = __float_as_uint(L[S16_NP_SHP + S16_SHP * ((pk >> 16) & 0xFF) + 14]), pb = __float_as_uint(L[S16_NP_SHP + S16_SHP * ((pk >> 24) & 0xFF) + 14]);
-          // bit 16: the manifold carries a torsional friction row (either shape has a patch radius)
-          const bool tors = fmaxf(L[S16_NP_SHP + S16_SHP * ((pk >> 16) & 0xFF) + 19], L[S16_NP_SHP + S16_SHP * ((pk >> 24) & 0xFF) + 19]) > 0.f;
-          key_[i] = (int)(((pa >> 10) & 31u) | (((pb >> 10) & 31u) << 8)) | (tors ? 1 << 16 : 0);
+        auto b16 = [&](bool v) __attribute__((always_inline)) { return (unsigned)(__ballot(v) >> (16 * g)) & 0xFFFFu; };
+        // one bit per manifold of the env (group-uniform) from the lanes' flags of their manifolds c, c + 16, c + 32, c + 48
+        auto b64 = [&](const bool (&v)[4]) __attribute__((always_inline)) {
+          return (unsigned long long)(b16(v[0]) | (b16(v[1]) << 16)) | ((unsigned long long)(b16(v[2]) | (b16(v[3]) << 16)) << 32);
+        };
+        // the words of the lane's own manifolds stay in registers through the pass: key, size, anchor << 4 | point mask. The
+        // LDS copies serve the reads of other lanes' manifolds.
+        int kyr[4], cnr[4], kpr[4];
+        bool touches_free = false;  // a hit of this env involves a free body
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int i = c + 16 * k;
+          kyr[k] = 0; cnr[k] = 0; kpr[k] = 0;
+          if (i < nh) {
+            const int pk = hit_[i];
+            const unsigned pa = __float_as_uint(L[S16_NP_SHP + S16_SHP * ((pk >> 16) & 0xFF) + 14]), pb = __float_as_uint(L[S16_NP_SHP + S16_SHP * ((pk >> 24) & 0xFF) + 14]);
+            // bit 16: the manifold carries a torsional friction row (either shape has a patch radius)
+            const bool tors = fmaxf(L[S16_NP_SHP + S16_SHP * ((pk >> 16) & 0xFF) + 19], L[S16_NP_SHP + S16_SHP * ((pk >> 24) & 0xFF) + 19]) > 0.f;
+            kyr[k] = (int)(((pa >> 10) & 31u) | (((pb >> 10) & 31u) << 8)) | (tors ? 1 << 16 : 0);
+            key_[i] = kyr[k];
+            cnr[k] = cnt_[i];
+            touches_free = touches_free || free_of((int)((pa >> 10) & 31u)) >= 0 || free_of((int)((pb >> 10) & 31u)) >= 0;
+          }
         }
-        WSYNC();
         // sleeping free bodies: a "disturber" is an articulation link or a free body that is awake and not calm. A
         // sleeping body touched by a disturber wakes; the manifolds of a body that stays asleep are dropped; whether a
         // disturber touched it feeds its sleep counter at the end of the substep.
-        {
+        // (without a hit that involves a free body nothing is disturbed, woken or dropped)
+        fdist = 0u;
+        if (nf > 0 && __any(touches_free)) {  // (wave-uniform)
           unsigned dist = 0u;  // bit b: free body b has a manifold with a disturber
-          auto free_of = [&](int slot1) { return (slot1 > S16_PT_FREE && slot1 <= S16_PT_FREE + S16_MAX_FREE) ? slot1 - 1 - S16_PT_FREE : -1; };
-          auto disturber = [&](int slot1) {
-            if (slot1 > S16_PT_LINK && slot1 <= S16_PT_FREE) return true;  // pose slots 1..16: articulation links
-            const int b = free_of(slot1);
-            return b >= 0 && fw_at(b) > 0.f && !fc_at(b);
-          };
-          for (int i = c; i < nh; i += 16) {
-            if (cnt_[i] <= 0) continue;
-            const int ky = key_[i];
-            const int s1a = ky & 31, s1b = (ky >> 8) & 31;
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            if (cnr[k] <= 0) continue;
+            const int s1a = kyr[k] & 31, s1b = (kyr[k] >> 8) & 31;
             const int ba = free_of(s1a), bb = free_of(s1b);
             if (ba >= 0 && disturber(s1b)) dist |= 1u << ba;
             if (bb >= 0 && disturber(s1a)) dist |= 1u << bb;
           }
-          dist |= __shfl_xor(dist, 8, 16); dist |= __shfl_xor(dist, 4, 16); dist |= __shfl_xor(dist, 2, 16); dist |= __shfl_xor(dist, 1, 16);
+          dist |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)dist, 0x128, 0xF, 0xF, false);  // row_ror 8, 4, 2, 1: every lane of the group
+          dist |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)dist, 0x124, 0xF, 0xF, false);
+          dist |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)dist, 0x122, 0xF, 0xF, false);
+          dist |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)dist, 0x121, 0xF, 0xF, false);
           if constexpr (NR > 1) dist = (unsigned)env_bci((int)dist, 0);  // (every lane of the env keeps the sleep counters)
           fdist = dist;
 #pragma unroll
           for (int b = 0; b < S16_MAX_FREE; b++)
             if (b < nf && fwake[b] <= 0.f && ((dist >> b) & 1u)) fwake[b] = MSSIM_WAKE_TIME;
-          for (int i = c; i < nh; i += 16) {
-            const int ky = key_[i];
-            const int ba = free_of(ky & 31), bb = free_of((ky >> 8) & 31);
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            const int i = c + 16 * k;
+            if (i >= nh) continue;
+            const int ba = free_of(kyr[k] & 31), bb = free_of((kyr[k] >> 8) & 31);
             const bool sa_ = ba >= 0 && fw_at(ba) <= 0.f, sb_ = bb >= 0 && fw_at(bb) <= 0.f;
-            if (sa_ || sb_) cnt_[i] = 0;
+            if (sa_ || sb_) { cnr[k] = 0; cnt_[i] = 0; }
           }
-          WSYNC();
         }
+        WSYNC();
         BT_T(8);
-        bool any_big = false;
+        // anchor search, every lane for its own manifolds (a walk of the candidates by the whole group, one broadcast read
+        // each, was measured and did not pay: DESIGN.md 3, round 4)
+        int anc[4];
+        bool hasp[4];
         for (int i = c; i < nh; i += 16) {
           int anchor = i;
           const int ci = cnt_[i];
@@ -2053,30 +2153,42 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
           }
           keep_[i] = (anchor << 4) | ((1 << ci) - 1);
         }
-        WSYNC();
-        BT_T(25);
-        // pass 1, the anchor's lane: size of its patch and whether it carries a torsional record
-        for (int a = c; a < nh; a += 16) {
-          if ((keep_[a] >> 4) != a || cnt_[a] == 0) continue;
-          int total = 0, tflag = 0;
-          for (int i = a; i < nh; i++) {
-            const bool mem = (keep_[i] >> 4) == a;
-            total += mem ? cnt_[i] : 0;
-            tflag |= (mem && cnt_[i] > 0) ? (key_[i] >> 16) & 1 : 0;
-          }
-          // bit 17 (anchors): the patch carries a torsional friction record; bit 18: more than 4 points, to be cut
-          key_[a] |= (tflag << 17) | (total > 4 ? 1 << 18 : 0);
-          any_big = any_big || total > 4;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int i = c + 16 * k;
+          hasp[k] = cnr[k] > 0;
+          kpr[k] = i < nh ? keep_[i] : i << 4;  // (the lane's own words)
+          anc[k] = kpr[k] >> 4;
         }
         WSYNC();
+        BT_T(25);
+        // pass 1, one anchor with points at a time: size of its patch and whether it carries a torsional record (sums over
+        // the group's lanes by DPP). Group-uniform masks, one bit per manifold: amask anchors with points, tmask those whose
+        // patch carries a torsional friction record, bmask those with more than 4 points, to be cut
+        bool isanc[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) isanc[k] = hasp[k] && anc[k] == c + 16 * k;
+        const unsigned long long amask = b64(isanc);
+        unsigned long long tmask = 0ull, bmask = 0ull;
+        for (unsigned long long m = amask; m; m &= m - 1ull) {  // (group-uniform)
+          const int a = __ffsll(m) - 1;
+          int t = 0;  // points | torsional manifolds << 16
+#pragma unroll
+          for (int k = 0; k < 4; k++) t += (hasp[k] && anc[k] == a) ? cnr[k] + (((kyr[k] >> 16) & 1) << 16) : 0;
+          t += __builtin_amdgcn_update_dpp(0, t, 0x128, 0xF, 0xF, false);
+          t += __builtin_amdgcn_update_dpp(0, t, 0x124, 0xF, 0xF, false);
+          t += __builtin_amdgcn_update_dpp(0, t, 0x122, 0xF, 0xF, false);
+          t += __builtin_amdgcn_update_dpp(0, t, 0x121, 0xF, 0xF, false);
+          if ((t >> 16) != 0) tmask |= 1ull << a;
+          if ((t & 0xFFFF) > 4) bmask |= 1ull << a;
+        }
         // pass 2, the whole group on one patch at a time: its candidate points in (manifold, point) order are spread over
         // the lanes (position p in lane p % 16), every scan of the selection rule is a group reduction -- the extremum,
         // then the lowest position within the tie tolerance of it ("first candidate wins", as the oracle's sequential scans)
-        if (__any(any_big)) {
+        if (__any(bmask != 0ull)) {
           unsigned short* const cl = reinterpret_cast<unsigned short*>(L + S16_NP_ML);  // (the stage B / C lists are dead) candidate: id | pool index << 8
-          auto b16 = [&](bool v) __attribute__((always_inline)) { return (unsigned)(__ballot(v) >> (16 * g)) & 0xFFFFu; };
-          for (int a = 0; a < nh; a++) {  // (group-uniform)
-            if (!((key_[a] >> 18) & 1)) continue;
+          for (unsigned long long bm = bmask; bm; bm &= bm - 1ull) {  // (group-uniform)
+            const int a = __ffsll(bm) - 1;
             const f3 na = f3{L[S16_NP_HN + 3 * a], L[S16_NP_HN + 3 * a + 1], L[S16_NP_HN + 3 * a + 2]};
             int n = 0;
             for (int base = a; base < nh; base += 16) {
@@ -2259,6 +2371,11 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
         BT_T(23);
         (void)0;
         WSYNC();
+        if (bmask != 0ull) {  // (the selection wrote the point masks of its patches' manifolds)
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+            if (c + 16 * k < nh) kpr[k] = keep_[c + 16 * k];
+        }
         // records in solver order: patch by patch (patches in the order of their anchors), inside a patch manifold by
         // manifold (a manifold belongs to one patch: the points of a shape pair stay together), then the patch's
         // torsional friction record if one of its shapes carries a patch radius (one solver block each,
@@ -2271,25 +2388,24 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
         float trr[4] = {-1.f, -1.f, -1.f, -1.f};  // (anchors) torsional radius of the patch, < 0: no torsional record
         int tot = 0;
         {
-          auto b16 = [&](bool v) __attribute__((always_inline)) { return (unsigned)(__ballot(v) >> (16 * g)) & 0xFFFFu; };
-          for (int a = 0; a < nh; a++) {  // (group-uniform)
-            if ((keep_[a] >> 4) != a || cnt_[a] == 0) continue;
-            const bool tpatch = (key_[a] >> 17) & 1;
+          for (unsigned long long m = amask; m; m &= m - 1ull) {  // (group-uniform)
+            const int a = __ffsll(m) - 1;
+            const bool tpatch = (tmask >> a) & 1ull;
             float tr = 0.f;
-            for (int base = a & ~15; base < nh; base += 16) {
-              const int i = base + c;
-              const int wi = i < nh ? keep_[i] : 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              if (16 * k + 15 < a || 16 * k >= nh) continue;  // (group-uniform)
+              const int i = 16 * k + c;
+              const int wi = kpr[k];
               const bool mem = i >= a && i < nh && (wi >> 4) == a;
               const int ni = mem ? __popc(wi & 15) : 0;
               const unsigned b0 = b16(ni & 1), b1 = b16(ni & 2), b2 = b16(ni & 4), lt = (1u << c) - 1u;
               const int pre = tot + __popc(b0 & lt) + 2 * __popc(b1 & lt) + 4 * __popc(b2 & lt);
-#pragma unroll
-              for (int k = 0; k < 4; k++)
-                if (mem && (base >> 4) == k) offs[k] = pre;
+              if (mem) offs[k] = pre;
               tot += __popc(b0) + 2 * __popc(b1) + 4 * __popc(b2);
               if (tpatch) {
                 float t = 0.f;
-                if (mem && cnt_[i] > 0 && ((key_[i] >> 16) & 1)) {
+                if (mem && cnr[k] > 0 && ((kyr[k] >> 16) & 1)) {
                   const int pkj = hit_[i];
                   t = fmaxf(L[S16_NP_SHP + S16_SHP * ((pkj >> 16) & 0xFF) + 19], L[S16_NP_SHP + S16_SHP * ((pkj >> 24) & 0xFF) + 19]);
                 }
@@ -2308,9 +2424,9 @@ __global__ __launch_bounds__(64 * S16_WAVES) void k_solve16(DevModel M, DevState
         for (int k = 0; k < 4; k++) {
           const int i = c + 16 * k;
           if (i >= nh) continue;
-          const int wi = keep_[i];
+          const int wi = kpr[k];
           const int mk = wi & 15, a = wi >> 4;
-          const bool is_anchor = a == i && cnt_[i] > 0;
+          const bool is_anchor = a == i && cnr[k] > 0;
           if (mk == 0 && !is_anchor) continue;
           int off = offs[k];
           const int off_end = offe[k];
