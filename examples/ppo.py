@@ -74,6 +74,8 @@ def main():
     ap.add_argument("--target-kl", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--partial-reset", action="store_true", help="stop episodes on success (default: ignore terminations)")
+    ap.add_argument("--save-video", default=None, metavar="DIR", help="after training, record the final policy's evaluation episodes as videos in DIR")
+    ap.add_argument("--num-eval-envs", type=int, default=16, help="envs of the recorded evaluation (tiled into one picture)")
     args = ap.parse_args()
 
     torch.manual_seed(args.seed)
@@ -165,6 +167,28 @@ def main():
             out["success_once"] = round(torch.cat(succ).mean().item(), 3)
             out["return"] = round(torch.cat(rets).mean().item(), 3)
         print(json.dumps(out), flush=True)
+    envs.close()
+    if args.save_video is not None:
+        record_evaluation(agent, args)
+
+
+def record_evaluation(agent, args):
+    """one episode of the final policy's mean action in a small batch of envs, recorded as a video of env.render()"""
+    from maniskill_amd.utils.wrappers.record import RecordEpisode
+
+    n = args.num_eval_envs
+    env = gym.make(args.env_id, num_envs=n, obs_mode="state", control_mode="pd_joint_delta_pos", sim_backend="physx_cuda", render_mode="rgb_array",
+                   human_render_camera_configs=dict(width=256, height=256))
+    env = RecordEpisode(env, args.save_video, save_trajectory=False, save_video=True, video_fps=20)
+    envs = ManiSkillVectorEnv(env, n, ignore_terminations=True, record_metrics=True)
+    obs, _ = envs.reset(seed=args.seed + 1)
+    done, info = False, {}
+    while not done:
+        with torch.no_grad():
+            obs, _, term, trunc, info = envs.step(torch.clamp(agent.actor_mean(obs), -1, 1))
+        done = bool(torch.logical_or(term, trunc).all())
+    if "final_info" in info:
+        print(json.dumps(dict(eval_success_once=round(info["final_info"]["episode"]["success_once"].float().mean().item(), 3), video_dir=args.save_video)), flush=True)
     envs.close()
 
 

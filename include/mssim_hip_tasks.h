@@ -415,6 +415,29 @@ int mssim_raycast_destroy(mssim_handle h, int32_t id);
  * depth_f32 optional device float [N][H][W]: t in metres, 0 where nothing is hit. */
 int mssim_raycast_render(mssim_handle h, int32_t id, int32_t camera, int16_t* pos_seg, float* depth_f32, void* stream);
 
+/* ---- A flat-shaded view of the same scene: what render() and the episode videos show -----------------------------
+ * A picture for people of the geometry the ray caster knows (collision shapes, plus whatever shapes the caller appended
+ * to the scene for the viewer): the nearest surface per pixel as above, its unit normal at the entry point, one colour
+ * per shape and two fixed lights. It is NOT the colour observation of a renderer with visual meshes and textures.
+ *   normal   plane +x; box: the axis whose slab set the entry parameter, signed against the ray (lowest axis on a tie);
+ *            sphere p / |p|; cylinder (+-1, 0, 0) where the cap slab set the entry, else (0, p_y, p_z) / r; capsule: of
+ *            whichever of its cylinder and two balls gave the earliest entry; hull: of the first plane in index order
+ *            that set the entry; triangle (e1 x e2) / |e1 x e2| turned to face the ray (two-sided, as for depth).
+ *   light    ambient 0.3, two white directional lights along (1, 1, -1) / sqrt 3 and (0, 0, -1) in the env frame, no
+ *            shadows, no specular term: c = albedo * min(1, 0.3 + sum_i max(0, -l_i . n)), byte = floor(255 min(c, 1) + 0.5).
+ *   albedo   rgb of the shape's colour; word 3 is a checker cell size w in metres (0: none): where
+ *            floor(p.x / w) + floor(p.y / w) + floor(p.z / w) is odd, p the entry point in the SHAPE frame (a plane's
+ *            p.x counts as exactly 0), the albedo is scaled by 0.8.
+ * mssim_raycast_set_colours: HOST arrays, copied. shape_rgba [n_shape][4]; env_shape_rgba [n_env_shape][N][4] (slot,
+ * then env) or NULL: a colour per env for the shapes in per-env slots, where actors of different sub-scenes share a body
+ * row. Refused (non-zero code, last_error text, tables unchanged): a negative or non-finite colour or cell size, a per-env
+ * table for a scene without per-env slots. It waits for the device and may allocate: not for the step loop.
+ * mssim_raycast_shade: one launch on the caller's stream, no host sync, no allocation. rgba_u8 device uint8 [N][H][W][4]:
+ * r, g, b, 255; a pixel that hits nothing gets one background colour. One 4-byte store per pixel: rgba_u8 must be 4-byte
+ * aligned. Refused: a bad id or camera, shading before any colours were set, a misaligned or missing output. */
+int mssim_raycast_set_colours(mssim_handle h, int32_t id, const float* shape_rgba, const float* env_shape_rgba);
+int mssim_raycast_shade(mssim_handle h, int32_t id, int32_t camera, uint8_t* rgba_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,7 +67,7 @@ class Device:
 
 
 class RenderMaterial:
-    """inert record (state observations only; no renderer in this build)"""
+    """a material as a record: `base_color` is what the shaded view of `env.render()` paints a shape with"""
 
     def __init__(self, base_color=(1, 1, 1, 1), **kw):
         self.base_color = list(base_color)

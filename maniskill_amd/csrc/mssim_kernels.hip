@@ -2283,6 +2283,7 @@ int mssim_overflow_count(mssim_handle h, void* stream) {
 
 #include "mssim_raycast_desc.h"  // what mssim_raycast_create accepts (host only)
 #include "mssim_raycast.h"       // the ray caster of the camera observations: k_raycast and the mssim_raycast_* entry points
+#include "mssim_raycast_shade.h" // its flat-shaded view for render(): k_raycast_shade, mssim_raycast_set_colours / _shade
 #include "mssim_test_collide.h"  // test hook, not part of the ABI: the manifold routines of k_solve16 on explicit shape pairs
 
 #ifdef MSSIM_PHASE_CLOCKS

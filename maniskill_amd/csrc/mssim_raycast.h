@@ -347,6 +347,9 @@ struct RcObject {
   std::vector<void*> allocs;
   bool needs_rows = false;  // some shape or camera rides on a body row
   bool mesh = false;        // the scene holds a triangle mesh, per-env plane ranges or per-env ids: k_raycast<true>
+  // the shaded view (mssim_raycast_shade.h): colour tables once mssim_raycast_set_colours was called, the slot count they are checked against
+  int n_env_shape = 0;
+  const float* rgba = nullptr; const float* env_rgba_store = nullptr; const float* env_rgba = nullptr;
   ~RcObject() { for (void* p : allocs) (void)hipFree(p); }
 };
 
@@ -450,6 +453,7 @@ int mssim_raycast_create(mssim_handle h, const mssim_raycast_scene* s, const mss
   }
   RcTables& T = o->T;
   T.n_shape = s->n_shape;
+  o->n_env_shape = s->n_env_shape;
   if (int rc = rc_upload(h, o.get(), s->shape_type, n, &T.type)) return rc;
   if (int rc = rc_upload(h, o.get(), s->shape_row, n, &T.row)) return rc;
   if (int rc = rc_upload(h, o.get(), s->shape_frame, 7 * n, &T.frame)) return rc;

@@ -8,7 +8,8 @@ API counterpart of mani_skill/envs/sapien_env.py (constructor :185-327, reset :7
     `sim_freq // control_freq` substeps of one control step are issued as ONE native call;
   * no rasteriser: the cameras cast rays at the collision geometry (maniskill_amd/sensors/camera.py). Obs modes are
     "state", "state_dict", "none", and "depth" / "segmentation" / "position" in any "+" combination, also with
-    "state" or "state_dict"; colour ("rgb", "rgbd", "pointcloud", ...) and `render()` are not available.
+    "state" or "state_dict"; colour observations ("rgb", "rgbd", "pointcloud", ...) are not available. `render()` gives a
+    flat-shaded view of the collision geometry (render_mode "rgb_array", "sensors" or "all").
 """
 import copy
 import gc
@@ -154,6 +155,7 @@ class BaseEnv(gym.Env):
         self.render_mode = render_mode
         self._sensors = dict()
         self._custom_sensor_configs = sensor_configs
+        self._custom_human_render_camera_configs = human_render_camera_configs
 
         self._main_seed = None
         from maniskill_amd.distributed import env_index_offset
@@ -765,9 +767,102 @@ class BaseEnv(gym.Env):
         self.set_state_dict(sd, env_idx)
 
     # ------------------------------------------------------------------ misc
+    # ------------------------------------------------------------------ render: a flat-shaded view for people
+    RENDER_BUDGET_ENV = "MS_RENDER_MAX_BYTES"
+    RENDER_BUDGET_DEFAULT = 8 << 30  # bytes of one camera's RGBA buffer, N x H x W x 4
+
+    def _check_render_budget(self, camera: Camera):
+        import os as _os
+
+        budget = int(_os.environ.get(self.RENDER_BUDGET_ENV, self.RENDER_BUDGET_DEFAULT))
+        need = self.num_envs * camera.height * camera.width * 4
+        if need > budget:
+            raise ValueError(f"a picture of camera {camera.uid!r} takes num_envs x height x width x 4 = {self.num_envs} x {camera.height} x {camera.width} x 4 = "
+                             f"{need} bytes, above the budget of {budget} ({self.RENDER_BUDGET_ENV}): lower num_envs, or the camera's size through "
+                             "human_render_camera_configs / sensor_configs (dict(width=..., height=...))")
+
+    def _human_render_cameras(self) -> Dict[str, Camera]:
+        """the task's `_default_human_render_camera_configs` with the user's `human_render_camera_configs` overrides
+        (the rules of `sensor_configs`), on a ray-cast rig of their own that also draws goal markers; created at the
+        first render, so that an env that never renders pays nothing"""
+        if getattr(self.scene, "_human_render_ready", False):
+            return self.scene.human_render_cameras
+        configs = cameras_by_uid(self._default_human_render_camera_configs)
+        if self._custom_human_render_camera_configs is not None:
+            apply_sensor_overrides(configs, self._custom_human_render_camera_configs, what="human_render_camera_configs")
+        rig = RaycastRig(self.scene, self._segmentation_ids_by_owner(), viewer=True)
+        robot = self.agent.robot if self.agent is not None else None
+        self.scene.human_render_cameras = {uid: Camera(config, self.scene, robot if config.entity_uid is not None else None, rig=rig) for uid, config in configs.items()}
+        self.scene._human_render_ready = True
+        return self.scene.human_render_cameras
+
+    def _pictures(self, cameras: Dict[str, Camera]) -> List[torch.Tensor]:
+        for cam in cameras.values():
+            self._check_render_budget(cam)
+        for cam in cameras.values():
+            cam.capture_picture()
+        return [cam.get_picture() for cam in cameras.values()]
+
+    def render_rgb_array(self, camera_name: Optional[str] = None) -> torch.Tensor:
+        """uint8 [N, H', W', 3]: the human render cameras' shaded views, tiled (one of them by name). Hidden objects
+        (goal markers) are shown, as the reference shows them in this mode."""
+        from maniskill_amd.utils.visualization.misc import tile_images
+
+        cameras = self._human_render_cameras()
+        if camera_name is not None:
+            if camera_name not in cameras:
+                raise KeyError(f"no human render camera {camera_name!r} (there are: {', '.join(cameras) or 'none'})")
+            cameras = {camera_name: cameras[camera_name]}
+        if not cameras:
+            raise RuntimeError(f"{type(self).__name__} declares no human render camera (_default_human_render_camera_configs)")
+        # a hidden object sits far away in the pose buffer: put its pose back for the picture alone (the simulation never sees it)
+        shown = [(o, o._rows()[:, :7].clone()) for o in self._hidden_objects if getattr(o, "hidden", False)]
+        for o, _ in shown:
+            o._write_rows(slice(0, 7), o.before_hide_pose)
+        try:
+            return tile_images(self._pictures(cameras))
+        finally:
+            for o, away in shown:
+                o._write_rows(slice(0, 7), away)
+
+    def render_sensors(self) -> torch.Tensor:
+        """uint8 [N, H', W', 3]: per sensor its shaded view beside its depth and segmentation pictures, tiled"""
+        from maniskill_amd.utils.visualization.misc import tile_images
+
+        if not self._sensors:
+            raise RuntimeError(f"{type(self).__name__} has no sensors to render")
+        pictures = self._pictures(self._sensors)
+        images = []
+        for cam, picture in zip(self._sensors.values(), pictures):
+            cam.capture()
+            views = camera_observations_to_images(cam.get_obs(depth=True, position=False, segmentation=True))
+            images += [picture, views["depth"], views["segmentation"]]
+        return tile_images(images)
+
+    def render_all(self) -> torch.Tensor:
+        from maniskill_amd.utils.visualization.misc import tile_images
+
+        images = [self.render_rgb_array()] if self._default_human_render_camera_configs else []
+        if self._sensors:
+            images.append(self.render_sensors())
+        return tile_images(images)
+
     def render(self):
-        raise NotImplementedError("render() needs colour, which this build lacks: its cameras cast rays at the collision geometry (obs modes depth / "
-                                  "segmentation / position; get_sensor_images() for pictures of those)")
+        """dispatches on `render_mode`: "rgb_array" (the human render cameras), "sensors", "all". The picture is a
+        flat-shaded view of the collision geometry for people to look at; colour OBSERVATIONS stay missing."""
+        mode = self.render_mode
+        if mode is None:
+            raise NotImplementedError("render() needs a render_mode: make the env with render_mode=\"rgb_array\", \"sensors\" or \"all\" for a flat-shaded view "
+                                      "of the collision geometry; colour observations (rgb, rgbd, pointcloud, ...) are still missing in this build")
+        if mode == "human":
+            raise NotImplementedError("render_mode=\"human\" needs a window system, which this build has none of; \"rgb_array\", \"sensors\" and \"all\" work")
+        if mode == "rgb_array":
+            return self.render_rgb_array()
+        if mode == "sensors":
+            return self.render_sensors()
+        if mode == "all":
+            return self.render_all()
+        raise NotImplementedError(f"Unsupported render mode {mode}. Must be one of {self.SUPPORTED_RENDER_MODES}")
 
     def print_sim_details(self):
         print("# -------------------------------------------------------------------------- #")

@@ -1,9 +1,9 @@
 """ManiSkillScene: owns the `px` system, the actor / articulation registry and the partial-reset mask.
 
 Counterpart of mani_skill/envs/scene.py (step :374-375, contact queries :736-796, state registry
-:819-892, _setup :897-939, _gpu_apply_all :941-957, _gpu_fetch_all :959-977). Rendering, cameras,
-lights and the viewer are out of scope (state observations only): the light / camera calls are
-accepted and ignored. There are no sub-scenes: every env shares one compiled model and has its own
+:819-892, _setup :897-939, _gpu_apply_all :941-957, _gpu_fetch_all :959-977). The sensors and the human
+render cameras live in `sensors` / `human_render_cameras` (ray-cast cameras, sensors/camera.py); the
+viewer is out of scope, and the light calls are accepted and ignored (the shaded view has two fixed lights). There are no sub-scenes: every env shares one compiled model and has its own
 coordinate frame, so no spacing offsets exist.
 """
 import contextlib

@@ -59,6 +59,15 @@ class SceneManipulationEnv(BaseEnv):
             return []
         return [CameraConfig("base_camera", sapien_utils.look_at([0.3, 0, 0.6], [-0.1, 0, 0.1]), 128, 128, np.pi / 2, 0.01, 100)]
 
+    @property
+    def _default_human_render_camera_configs(self):
+        """with the Fetch: one camera above a corner of the room and one riding on the robot's torso, looking back at it;
+        otherwise one on the arm's workspace (base_env.py:161-191 of the reference)"""
+        if self.robot_uids == "fetch":
+            return [CameraConfig("render_camera", sapien_utils.look_at([2.5, -2.5, 3], [0.0, 0.0, 0]), 512, 512, 1, 0.01, 100),
+                    CameraConfig("robot_render_camera", sapien_utils.look_at([2, 0, 1], [0, 0, -1]), 512, 512, 1.5, 0.01, 100, mount=self.agent.torso_lift_link)]
+        return CameraConfig("render_camera", sapien_utils.look_at([0.4, 0.4, 0.8], [0.0, 0.0, 0.4]), 512, 512, 1, 0.01, 100)
+
     def _load_lighting(self, options: dict):
         if not self.scene_builder.builds_lighting:
             super()._load_lighting(options)

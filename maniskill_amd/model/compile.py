@@ -52,6 +52,7 @@ class ShapeRecord:
     min_patch_radius: float = 0.0
     density: float = 1000.0
     collision_groups: Sequence[int] = (1, 1, 0, 0)
+    color: Optional[Sequence[float]] = None  # r, g, b for the shaded view (`raycast_colours`); None: a default by owner
 
     def param(self):
         if self.type == "box":
@@ -125,6 +126,10 @@ class ActorRecord:
     # ShapeRecords per env, e.g. PegInsertionSide's pegs and boxes-with-hole built per sub-scene and
     # merged (reference: Actor.merge, utils/structs/actor.py:99-126)
     env_shapes: Optional[List[List[ShapeRecord]]] = None
+    # visual primitives (ShapeRecords with a colour) of a body whose visuals are not its collision shapes one for one: a
+    # goal marker without any collision shape, a peg of one box painted in two halves. The viewer's ray-cast scene draws
+    # them in place of the body's collision shapes (`raycast_viewer_scene`); the simulation and the sensors never see them
+    visuals: List[ShapeRecord] = field(default_factory=list)
 
 
 @dataclass
@@ -154,6 +159,10 @@ class CompiledModel:
     static_names: List[str]
     shape_owner: List[str]
     n_rows: int
+    # for the shaded view: per compiled shape (colour of the shared record, [colour per env] or None), and the bodies
+    # whose visual primitives the viewer draws instead of their collision shapes: dict(owner, body_type, initial_pose, visuals)
+    shape_colors: List[tuple] = field(default_factory=list)
+    visual_bodies: List[dict] = field(default_factory=list)
 
     @property
     def n_dof(self):
@@ -215,6 +224,8 @@ def shapes_from_urdf_link(link, materials=None, link_cfg=None, max_hull_verts=MA
             s.min_patch_radius = float(cfg["min_patch_radius"])
         if "density" in cfg:
             s.density = float(cfg["density"])
+        if getattr(link, "color", None) is not None:
+            s.color = tuple(float(x) for x in link.color)
         out.append(s)
     return out
 
@@ -653,6 +664,9 @@ class SceneModelBuilder:
             static_names=static_names,
             shape_owner=[s["owner"] for s in shapes],
             n_rows=n_link + n_free + n_kin,
+            shape_colors=[(s["rec"].color, None if s.get("env") is None else [r.color for r in s["env"]]) for s in shapes],
+            visual_bodies=[dict(owner=a.name, body_type=a.body_type, initial_pose=a.initial_pose, visuals=list(a.visuals))
+                           for a in self.actors if a.visuals and a.env_shapes is None and len(a.visuals) != len(a.shapes)],
         )
 
 
@@ -741,3 +755,89 @@ def raycast_scene(model: CompiledModel, seg_ids: Dict[str, object], meshes: bool
     if per_env_ids:
         out["env_shape_seg"] = env_seg
     return out
+
+
+# default colours of the shaded view (r, g, b), for shapes whose builder recorded no visual
+ROBOT_GREY = (0.75, 0.75, 0.78)
+TABLE_WOOD = (0.62, 0.46, 0.30)
+GROUND_GREY = (0.55, 0.55, 0.55)
+GROUND_CELL = 1.0  # metres: the ground is a checkered board, so that a moving base can be seen to move
+WALL_COLOUR = (0.85, 0.82, 0.75)
+
+
+def raycast_colours(model: CompiledModel, seg_ids: Dict[str, object]) -> Dict[str, np.ndarray]:
+    """The colour tables of `raycast_scene(model, seg_ids, ...)` for the shaded view (`mssim_raycast_set_colours`):
+    `shape_rgba` f32 [n_shape, 4] -- r, g, b and a checker cell size in metres, 0 for none -- and, where a per-env slot's
+    colour differs from env to env, `env_shape_rgba` f32 [n_env_shape, N, 4]. A shape takes the colour its builder
+    recorded (`ShapeRecord.color`: the visual's base colour, a URDF link's material colour); without one a default: light
+    grey for robot links, the checkered grey for a ground plane, a wood tone for the table, a wall colour for other static
+    scenery, and for anything else the palette of `sensors.camera.id_colours` at its segmentation id (of the env's own id
+    where `seg_ids` has one per env), so that distinct objects differ."""
+    from maniskill_amd.sensors.camera import _ID_COLOUR
+
+    A, N = model.arrays, int(model.scalars["num_envs"])
+    ns, n_es = int(model.scalars["n_shape"]), int(model.scalars["n_env_shape"])
+    types, slots = A["shape_type"], A["shape_env_slot"]
+    recorded = model.shape_colors if model.shape_colors else [(None, None)] * ns
+
+    def default(owner, is_plane, seg):
+        if owner in model.link_names:
+            return (*ROBOT_GREY, 0.0)
+        if is_plane:
+            return (*GROUND_GREY, GROUND_CELL)
+        if owner.startswith("table"):
+            return (*TABLE_WOOD, 0.0)
+        if owner in model.static_names or seg == 0:
+            return (*WALL_COLOUR, 0.0)
+        return (*[(int(seg) * m % 256) / 255.0 for m in _ID_COLOUR], 0.0)
+
+    def rgba_of(color, owner, is_plane, seg):
+        return (*[float(x) for x in color[:3]], 0.0) if color is not None else default(owner, is_plane, seg)
+
+    rgba, env = np.zeros((ns, 4), dtype=np.float32), np.zeros((n_es, N, 4), dtype=np.float32)
+    per_env = False
+    for i in range(ns):
+        owner, (shared, by_env) = model.shape_owner[i], recorded[i]
+        ids = seg_ids.get(owner, 0)
+        seg = int(ids) if np.ndim(ids) == 0 else int(np.asarray(ids)[np.argmax(np.asarray(ids) != 0)])
+        rgba[i] = rgba_of(shared, owner, types[i] == SHAPE_PLANE, seg)
+        if slots[i] < 0:
+            continue
+        for e in range(N):
+            seg_e = seg if np.ndim(ids) == 0 else int(np.asarray(ids)[e])
+            env[slots[i], e] = rgba_of(by_env[e] if by_env is not None and by_env[e] is not None else shared, owner, False, seg_e)
+        per_env = per_env or bool((env[slots[i]] != rgba[i]).any())
+    out = dict(shape_rgba=rgba)
+    if per_env:
+        out["env_shape_rgba"] = env
+    return out
+
+
+def raycast_viewer_scene(model: CompiledModel, seg_ids: Dict[str, object]):
+    """(scene, colours) of the viewer (`render_mode="rgb_array"`): `raycast_scene(model, seg_ids, meshes=True)` with its
+    `raycast_colours`, and appended to both the visual primitives of the bodies whose visuals are not their collision
+    shapes one for one (`CompiledModel.visual_bodies`: a goal marker without any shape, a two-coloured peg), each on its
+    body's row and in its recorded colour; such a body's own collision shapes are left out (MSSIM_SHAPE_NONE). The
+    sensors' scene never holds them. Translucency is not supported: they are drawn opaque."""
+    scene, colours = dict(raycast_scene(model, seg_ids, meshes=True)), dict(raycast_colours(model, seg_ids))
+    scene["shape_type"] = np.array(scene["shape_type"])
+    for body in model.visual_bodies:
+        scene["shape_type"][[i for i, o in enumerate(model.shape_owner) if o == body["owner"]]] = SHAPE_NONE
+    extra = dict(shape_type=[], shape_row=[], shape_frame=[], shape_param=[], shape_bound=[], shape_seg=[], shape_planes=[], shape_env_slot=[], rgba=[])
+    for body in model.visual_bodies:
+        row = model.row_of(body["owner"])
+        ids = seg_ids.get(body["owner"], 0)
+        for v in body["visuals"]:
+            frame = v.pose if row >= 0 else geom.compose(body["initial_pose"], v.pose)
+            c, r = v.bound()
+            extra["shape_type"].append(_SHAPE_NAMES[v.type]); extra["shape_row"].append(row); extra["shape_frame"].append(frame)
+            extra["shape_param"].append(v.param()); extra["shape_bound"].append([*geom.transform_point(np.asarray(frame, dtype=np.float64), c), r])
+            extra["shape_seg"].append(int(ids) if np.ndim(ids) == 0 else 0); extra["shape_planes"].append([0, 0]); extra["shape_env_slot"].append(-1)
+            extra["rgba"].append([*(v.color if v.color is not None else WALL_COLOUR)][:3] + [0.0])
+    if extra["shape_type"]:
+        for key in ("shape_type", "shape_row", "shape_frame", "shape_param", "shape_bound", "shape_seg", "shape_planes", "shape_env_slot"):
+            old = np.asarray(scene[key])
+            new = np.asarray(extra[key], dtype=old.dtype).reshape((-1,) + old.shape[1:])
+            scene[key] = np.ascontiguousarray(np.concatenate([old, new]))
+        colours["shape_rgba"] = np.concatenate([colours["shape_rgba"], np.asarray(extra["rgba"], dtype=np.float32)])
+    return scene, colours

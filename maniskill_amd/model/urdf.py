@@ -51,6 +51,8 @@ class LinkRecord:
     inertia: np.ndarray = field(default_factory=lambda: np.zeros((3, 3)))  # about com, link frame
     has_inertial: bool = False
     collisions: List[CollisionRecord] = field(default_factory=list)
+    color: Optional[np.ndarray] = None  # rgb of the first <visual><material><color>, where the file spells one out
+
 
 
 @dataclass
@@ -105,6 +107,9 @@ def parse_urdf(urdf_file: str, srdf_file: Optional[str] = None) -> RobotDescript
                 )
             R = geom.quat_to_mat(T[3:])
             lr.mass, lr.com, lr.inertia, lr.has_inertial = m, T[:3].copy(), R @ I @ R.T, True
+        ce = le.find("visual/material/color")
+        if ce is not None and ce.get("rgba"):
+            lr.color = _floats(ce.get("rgba"), 4)[:3]
         for ce in le.findall("collision"):
             ge = ce.find("geometry")
             if ge is None:

@@ -349,6 +349,8 @@ class NativeLib:
             ("raycast_create", C.c_int, [H, C.POINTER(RaycastScene), C.POINTER(CameraDesc), C.c_int32, _I32P]),
             ("raycast_destroy", C.c_int, [H, C.c_int32]),
             ("raycast_render", C.c_int, [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("raycast_set_colours", C.c_int, [H, C.c_int32, _F32P, _F32P]),
+            ("raycast_shade", C.c_int, [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
         ):
             if hasattr(self.lib, self.prefix + name):
                 self._fn(name, restype, argtypes)
@@ -588,6 +590,20 @@ class NativeSim:
         if self.lib.raycast_render is None:
             raise NativeError(f"{self.lib.path} has no raycast_render (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.raycast_render(self.h, int(rid), int(camera), pos_seg_ptr, depth_ptr, stream), "raycast_render")
+
+    def raycast_set_colours(self, rid: int, shape_rgba, env_shape_rgba=None):
+        """host arrays, copied by the call: shape_rgba [n_shape, 4] (r, g, b, checker cell size in metres), env_shape_rgba
+        [n_env_shape, N, 4] or None"""
+        if self.lib.raycast_set_colours is None:
+            raise NativeError(f"{self.lib.path} has no raycast_set_colours (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        a = np.ascontiguousarray(shape_rgba, dtype=np.float32).reshape(-1, 4)
+        e = None if env_shape_rgba is None else np.ascontiguousarray(env_shape_rgba, dtype=np.float32)
+        self._check(self.lib.raycast_set_colours(self.h, int(rid), a.ctypes.data_as(_F32P), None if e is None else e.ctypes.data_as(_F32P)), "raycast_set_colours")
+
+    def raycast_shade(self, rid: int, camera: int, rgba_ptr, stream=None):
+        if self.lib.raycast_shade is None:
+            raise NativeError(f"{self.lib.path} has no raycast_shade (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.raycast_shade(self.h, int(rid), int(camera), rgba_ptr, stream), "raycast_shade")
 
     def task_pick_outputs(self, task: "PickTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
         self._check(self.lib.task_pick_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_pick_outputs")

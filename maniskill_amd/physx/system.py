@@ -468,6 +468,27 @@ class MssimSystem:
         assert depth is None or (depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (self.num_envs, h, w))
         self._sim.raycast_render(rid, camera, pos_seg.data_ptr(), None if depth is None else depth.data_ptr(), self._stream())
 
+    def raycast_set_colours(self, rid: int, shape_rgba: np.ndarray, env_shape_rgba: Optional[np.ndarray] = None):
+        """the colours of a ray-cast scene's shapes for `raycast_shade` (`model.compile.raycast_colours`): host arrays
+        shape_rgba f32 [n_shape, 4] -- r, g, b in [0, 1] and a checker cell size in metres, 0 for none -- and optionally
+        env_shape_rgba f32 [n_env_shape, N, 4], a colour per env for the shapes in per-env slots"""
+        self._raycast_sizes(rid)
+        if env_shape_rgba is not None:
+            env_shape_rgba = np.asarray(env_shape_rgba, dtype=np.float32)
+            if env_shape_rgba.ndim != 3 or env_shape_rgba.shape[1:] != (self.num_envs, 4):
+                raise native.NativeError(f"raycast_set_colours: env_shape_rgba must be [slots, {self.num_envs}, 4], got {tuple(env_shape_rgba.shape)}")
+        self._sim.raycast_set_colours(rid, shape_rgba, env_shape_rgba)
+
+    def raycast_shade(self, rid: int, camera: int, rgba: torch.Tensor):
+        """one launch on the current stream: the flat-shaded view of camera `camera` into `rgba` uint8 [N, H, W, 4]
+        (r, g, b, 255; the background colour where nothing is hit). Colours come first (`raycast_set_colours`)."""
+        sizes = self._raycast_sizes(rid)
+        if not 0 <= camera < len(sizes):
+            raise native.NativeError(f"raycast_shade: scene {rid} has no camera {camera} (it has {len(sizes)})")
+        w, h = sizes[camera]
+        assert rgba.dtype == torch.uint8 and rgba.is_contiguous() and tuple(rgba.shape) == (self.num_envs, h, w, 4)
+        self._sim.raycast_shade(rid, camera, rgba.data_ptr(), self._stream())
+
     def raycast_destroy(self, rid: int):
         self._raycast_sizes(rid)
         self._sim.raycast_destroy(rid)

@@ -2,11 +2,15 @@
 
 `CameraConfig` is the record task and robot files construct (camera.py:33-68 of the reference). `Camera` renders the
 geometric modalities -- depth, actor-level segmentation, camera-frame position -- by casting rays at the compiled
-model's collision geometry (include/mssim_hip_tasks.h `mssim_raycast_*`): there are no visual meshes, lights or
-colours in this build. One launch per camera fills one `int16 [N, H, W, 4]` buffer in the layout of the reference's
-minimal shader (x, y, z in millimetres in the camera's OpenGL frame, then the segmentation id). `get_obs` returns
-`position` and `segmentation` as views of that buffer, which the next capture overwrites (copy what you keep across
-steps), and `depth` as a tensor of its own.
+model's collision geometry (include/mssim_hip_tasks.h `mssim_raycast_*`): there are no visual meshes or textures
+in this build, and no colour OBSERVATIONS. One launch per camera fills one `int16 [N, H, W, 4]` buffer in the layout of the
+reference's minimal shader (x, y, z in millimetres in the camera's OpenGL frame, then the segmentation id). `get_obs`
+returns `position` and `segmentation` as views of that buffer, which the next capture overwrites (copy what you keep
+across steps), and `depth` as a tensor of its own.
+
+`capture_picture` / `get_picture` give a picture for people: the same geometry flat-shaded, one colour per shape under
+two fixed lights (`mssim_raycast_shade`). That is what `env.render()` and the episode videos show. It is not the
+reference's rendered `rgb` and is not handed out under that key: `get_obs(rgb=True)` keeps raising.
 """
 import copy
 from dataclasses import dataclass
@@ -52,20 +56,20 @@ def cameras_by_uid(declared) -> Dict[str, CameraConfig]:
 _CONFIG_FIELDS = frozenset(CameraConfig.__dataclass_fields__)
 
 
-def apply_sensor_overrides(cameras: Dict[str, CameraConfig], overrides: Dict[str, object]) -> None:
-    """The user's `sensor_configs` applied in place. A key that is a camera's uid holds a dict of field overrides for
+def apply_sensor_overrides(cameras: Dict[str, CameraConfig], overrides: Dict[str, object], what: str = "sensor_configs") -> None:
+    """The user's `sensor_configs` (or, under that name in `what`, `human_render_camera_configs`) applied in place. A key that is a camera's uid holds a dict of field overrides for
     that camera; any other key is a field set on every camera. Per-camera values win over the ones for all. A pose may
     be a Pose or seven numbers (p, q(wxyz): what a json-serialisable `gym.make` argument can carry)."""
 
     def checked(fields: dict, where: str) -> dict:
         unknown = sorted(set(fields) - _CONFIG_FIELDS)
         if unknown:
-            raise AttributeError(f"sensor_configs{where}: CameraConfig has no field {', '.join(unknown)} (its fields: {', '.join(sorted(_CONFIG_FIELDS))})")
+            raise AttributeError(f"{what}{where}: CameraConfig has no field {', '.join(unknown)} (its fields: {', '.join(sorted(_CONFIG_FIELDS))})")
         out = dict(fields)
         if isinstance(out.get("pose"), (list, tuple)):
             p = [float(x) for x in out["pose"]]
             if len(p) != 7:
-                raise ValueError(f"sensor_configs{where}: a pose given as numbers is p(3), q(4), got {len(p)} numbers")
+                raise ValueError(f"{what}{where}: a pose given as numbers is p(3), q(4), got {len(p)} numbers")
             out["pose"] = Pose.create_from_pq(p=p[:3], q=p[3:])
         return out
 
@@ -73,7 +77,7 @@ def apply_sensor_overrides(cameras: Dict[str, CameraConfig], overrides: Dict[str
     for uid, config in cameras.items():
         own = overrides.get(uid, {})
         if not isinstance(own, dict):
-            raise TypeError(f"sensor_configs[{uid!r}] must be a dict of CameraConfig fields")
+            raise TypeError(f"{what}[{uid!r}] must be a dict of CameraConfig fields")
         for field, value in {**for_all, **checked(own, f"[{uid!r}]")}.items():
             setattr(config, field, copy.deepcopy(value))
         config.pose = Pose.create(config.pose)
@@ -87,24 +91,44 @@ _GL_TO_CV = np.diag([1.0, -1.0, -1.0, 1.0])
 class RaycastRig:
     """The cameras of one env object on one native ray-cast scene. The scene (hull face planes, triangle meshes with
     their BVH, segmentation ids) is built and uploaded at the first capture, so that an env that never looks through its
-    cameras pays nothing."""
+    cameras pays nothing; the colour tables of the shaded view are built and uploaded at the first picture. `viewer`: the
+    scene also draws the visual primitives of bodies whose visuals are not their collision shapes (a goal marker), as the
+    human render cameras do; the sensors' scene holds collision geometry alone."""
 
-    def __init__(self, scene, seg_ids: Dict[str, int]):
-        self.scene, self.seg_ids = scene, seg_ids
+    def __init__(self, scene, seg_ids: Dict[str, int], viewer: bool = False):
+        self.scene, self.seg_ids, self.viewer = scene, seg_ids, viewer
         self.cameras: List["Camera"] = []
         self._id = None
+        self._colours = None
 
     def add(self, camera: "Camera") -> int:
         assert self._id is None, "cameras are added before the first capture"
         self.cameras.append(camera)
         return len(self.cameras) - 1
 
+    def _create(self):
+        if self._id is None:
+            from maniskill_amd.model.compile import raycast_colours, raycast_scene, raycast_viewer_scene
+
+            if self.viewer:
+                arrays, self._colours = raycast_viewer_scene(self.scene.model, self.seg_ids)
+            else:
+                arrays, self._colours = raycast_scene(self.scene.model, self.seg_ids, meshes=True), raycast_colours(self.scene.model, self.seg_ids)
+            self._id = self.scene.px.raycast_create(arrays, [c._desc() for c in self.cameras])
+        return self._id
+
+    def shade(self, camera: "Camera"):
+        px, rid = self.scene.px, self._create()
+        if self._colours is not None:  # (uploaded once, at the first picture)
+            px.raycast_set_colours(rid, self._colours["shape_rgba"], self._colours.get("env_shape_rgba"))
+            self._colours = None
+        if camera._rgba is None:
+            camera._rgba = torch.zeros((self.scene.num_envs, camera.height, camera.width, 4), dtype=torch.uint8, device=self.scene.device)
+        px.raycast_shade(rid, camera._index, camera._rgba)
+
     def render(self, camera: "Camera"):
         px = self.scene.px
-        if self._id is None:
-            from maniskill_amd.model.compile import raycast_scene
-
-            self._id = px.raycast_create(raycast_scene(self.scene.model, self.seg_ids, meshes=True), [c._desc() for c in self.cameras])
+        self._create()
         if camera._pos_seg is None:
             camera._pos_seg = torch.zeros((self.scene.num_envs, camera.height, camera.width, 4), dtype=torch.int16, device=self.scene.device)
         px.raycast_render(self._id, camera._index, camera._pos_seg)
@@ -138,6 +162,7 @@ class Camera:
         self._local = cfg.pose.raw_pose.to(device=dev, dtype=torch.float32)
         assert len(self._local) in (1, N), f"{cfg.uid}: one pose, or one per env"
         self._pos_seg = None  # int16 [N, H, W, 4], allocated at the first capture
+        self._rgba = None     # uint8 [N, H, W, 4], allocated at the first picture
         self._rig = rig
         self._index = rig.add(self) if rig is not None else None
 
@@ -159,6 +184,16 @@ class Camera:
         """one ray-cast launch on the current stream, from the pose buffers as they are (after the fetch)"""
         self._rig.render(self)
 
+    def capture_picture(self):
+        """one shading launch on the current stream, from the pose buffers as they are: the flat-shaded view"""
+        self._rig.shade(self)
+
+    def get_picture(self) -> torch.Tensor:
+        """uint8 [N, H, W, 3]: the shaded view of the last `capture_picture`, a VIEW of the camera's RGBA buffer (the next
+        picture overwrites it). A picture for people, not the `rgb` observation of a renderer."""
+        assert self._rgba is not None, f"{self.uid}: capture_picture() first"
+        return self._rgba[..., :3]
+
     def get_obs(self, rgb: bool = False, depth: bool = True, position: bool = True, segmentation: bool = True, normal: bool = False,
                 albedo: bool = False, apply_texture_transforms: bool = True) -> Dict[str, torch.Tensor]:
         """the captured image, in the dtypes and shapes of the reference's minimal shader:
@@ -168,7 +203,8 @@ class Camera:
                      overwrites it, copy what you keep.
         segmentation int16 [N, H, W, 1] `per_scene_id`, 0 = background. A VIEW of the buffer, as position."""
         if rgb or normal or albedo:
-            raise NotImplementedError("this build's cameras cast rays at geometry: depth, segmentation and position; colour (rgb, normal, albedo) is missing")
+            raise NotImplementedError("this build's cameras cast rays at geometry: depth, segmentation and position; colour (rgb, normal, albedo) is missing "
+                                      "as an observation (get_picture() is a flat-shaded view for people, not a renderer's rgb)")
         assert self._pos_seg is not None, f"{self.uid}: capture() first"
         out = {}
         if depth:

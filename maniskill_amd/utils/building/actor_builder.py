@@ -1,8 +1,12 @@
 """ActorBuilder: records collision shapes and registers ONE batched actor record with the scene.
 
 Counterpart of mani_skill/utils/building/actor_builder.py:31-260 (which subclasses
-`sapien.ActorBuilder` and builds one entity per sub-scene). Visual shapes are accepted and
-dropped: this build has no renderer (state observations only).
+`sapien.ActorBuilder` and builds one entity per sub-scene). Visual primitives (box, sphere, capsule,
+cylinder) are recorded with their pose, sizes and the material's base colour: the shaded view behind
+`env.render()` colours a collision shape with the visual at the same position in its builder (the
+first visual where the two lists differ in length); where they differ -- a goal marker without any
+collision shape, a peg of one box painted in two halves -- the viewer draws the visuals themselves.
+Visual meshes from files are accepted and ignored.
 """
 from typing import List, Optional, Sequence, Union
 
@@ -26,6 +30,7 @@ class ActorBuilder:
         self.physx_body_type = "dynamic"
         self.collision_groups = [1, 1, 0, 0]
         self.collision_shapes: List[pxc.PhysxCollisionShape] = []  # in the order of the add_*_collision calls
+        self.visual_records: List[ShapeRecord] = []  # in the order of the add_*_visual calls, each with its colour
         self.scene_idxs = None
         self._mass = None
         self._cmass_local_pose = None
@@ -70,8 +75,17 @@ class ActorBuilder:
 
     @property
     def shapes(self) -> List[ShapeRecord]:
-        """the recorded shapes as model-compiler records"""
-        return [s.to_record() for s in self.collision_shapes]
+        """the recorded shapes as model-compiler records, coloured by the recorded visuals"""
+        return self._coloured([s.to_record() for s in self.collision_shapes])
+
+    def _coloured(self, records: List[ShapeRecord]) -> List[ShapeRecord]:
+        """a collision shape takes the colour of the visual at its position when there are as many visuals as shapes,
+        otherwise that of the first visual; without visuals it keeps None (a default by owner, model/compile.py)"""
+        v = self.visual_records
+        for k, rec in enumerate(records):
+            if v:
+                rec.color = v[k].color if len(v) == len(records) else v[0].color
+        return records
 
     def _attach(self, shape: pxc.PhysxCollisionShape, pose, density, patch_radius, min_patch_radius):
         """every add_*_collision call ends here: the shape object gets what the reference sets on it just before
@@ -133,18 +147,34 @@ class ActorBuilder:
         """triangle-mesh collision for static / kinematic bodies (actor_builder.py:136-150)"""
         return self._attach(pxc.PhysxCollisionShapeTriangleMesh(filename, scale, self._mat(material)), pose, 0.0, patch_radius, min_patch_radius)
 
-    # -- visuals: accepted, ignored -------------------------------------------------------
-    def add_box_visual(self, *a, **kw):
+    # -- visuals: primitives are recorded for the shaded view, files are ignored ------------
+    @staticmethod
+    def _base_colour(material):
+        """r, g, b of a `sapien.render.RenderMaterial` (its `base_color`) or of a plain rgb(a) sequence; None: white"""
+        if material is None:
+            return (1.0, 1.0, 1.0)
+        c = getattr(material, "base_color", material)
+        c = [float(x) for x in np.asarray(common.to_numpy(c), dtype=np.float64).reshape(-1)]
+        if len(c) not in (3, 4) or not all(np.isfinite(c)) or min(c) < 0:
+            raise ValueError(f"a visual's material is a RenderMaterial or r, g, b(, a) >= 0, got {material!r}")
+        return tuple(c[:3])
+
+    def _visual(self, type_, pose, material, **sizes):
+        p = geom.pose() if pose is None else np.asarray(common.to_numpy(Pose.create(pose).raw_pose), dtype=np.float64).reshape(-1)[:7]
+        self.visual_records.append(ShapeRecord(type_, p, color=self._base_colour(material), **sizes))
         return self
 
-    def add_sphere_visual(self, *a, **kw):
-        return self
+    def add_box_visual(self, pose=None, half_size=(1, 1, 1), material=None, name=""):
+        return self._visual("box", pose, material, half_size=np.asarray(half_size, dtype=np.float64))
 
-    def add_capsule_visual(self, *a, **kw):
-        return self
+    def add_sphere_visual(self, pose=None, radius=1, material=None, name=""):
+        return self._visual("sphere", pose, material, radius=float(radius))
 
-    def add_cylinder_visual(self, *a, **kw):
-        return self
+    def add_capsule_visual(self, pose=None, radius=1, half_length=1, material=None, name=""):
+        return self._visual("capsule", pose, material, radius=float(radius), half_length=float(half_length))
+
+    def add_cylinder_visual(self, pose=None, radius=1, half_length=1, material=None, name=""):
+        return self._visual("cylinder", pose, material, radius=float(radius), half_length=float(half_length))
 
     def add_visual_from_file(self, *a, **kw):
         return self
@@ -172,6 +202,9 @@ class ActorBuilder:
             # per-env initial poses: the model keeps env 0's pose; the rest are written after gpu_init
             pass
         rec = comp.to_record(self.name, geom.pose(raw[0, :3], raw[0, 3:]))
+        self._coloured(rec.shapes)
+        if len(self.visual_records) != len(rec.shapes):  # the visuals say more (or other things) than the shapes: the viewer draws them
+            rec.visuals = list(self.visual_records)
         mass = 0.0
         if self.physx_body_type == "dynamic":
             mass = rec.mass if rec.mass is not None else sum(sr.mass_properties()[0] for sr in rec.shapes)

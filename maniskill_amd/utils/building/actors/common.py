@@ -1,21 +1,21 @@
 """Primitive actors by one call (same call signatures as mani_skill/utils/building/actors/common.py).
 
-Every helper is the same three steps -- a builder, one collision primitive (the visual twin is accepted and dropped:
-this build has no renderer), build as dynamic / static / kinematic -- so they share `_primitive_actor`, which is
-told the primitive by the name of the builder method and its arguments.
+Every helper is the same three steps -- a builder, one collision primitive with its visual twin in the helper's
+`color` (what the shaded view of `env.render()` paints the shape with), build as dynamic / static / kinematic -- so they
+share `_primitive_actor`, which is told the primitive by the name of the builder method and its arguments.
 """
 from typing import Optional  # noqa: F401
 
 _BUILD_METHOD = {"dynamic": "build", "static": "build_static", "kinematic": "build_kinematic"}
 
 
-def _primitive_actor(scene, name: str, body_type: str, add_collision: bool, scene_idxs, initial_pose, primitive: str, **geometry):
+def _primitive_actor(scene, name: str, body_type: str, add_collision: bool, scene_idxs, initial_pose, primitive: str, color=None, **geometry):
     if body_type not in _BUILD_METHOD:
         raise ValueError(f"Unknown body type {body_type}")
     builder = scene.create_actor_builder()
     if add_collision:
         getattr(builder, f"add_{primitive}_collision")(**geometry)
-    getattr(builder, f"add_{primitive}_visual")(**geometry)
+    getattr(builder, f"add_{primitive}_visual")(material=color, **geometry)
     if scene_idxs is not None:
         builder.set_scene_idxs(scene_idxs)
     if initial_pose is not None:
@@ -24,25 +24,41 @@ def _primitive_actor(scene, name: str, body_type: str, add_collision: bool, scen
 
 
 def build_cube(scene, half_size: float, color, name: str, body_type: str = "dynamic", add_collision: bool = True, scene_idxs=None, initial_pose=None):
-    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "box", half_size=[half_size] * 3)
+    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "box", color=color, half_size=[half_size] * 3)
 
 
 def build_box(scene, half_sizes, color, name: str, body_type: str = "dynamic", add_collision: bool = True, scene_idxs=None, initial_pose=None):
-    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "box", half_size=half_sizes)
+    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "box", color=color, half_size=half_sizes)
 
 
 def build_cylinder(scene, radius: float, half_length: float, color, name: str, body_type: str = "dynamic", add_collision: bool = True, scene_idxs=None, initial_pose=None):
-    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "cylinder", radius=radius, half_length=half_length)
+    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "cylinder", color=color, radius=radius, half_length=half_length)
 
 
 def build_sphere(scene, radius: float, color, name: str, body_type: str = "dynamic", add_collision: bool = True, scene_idxs=None, initial_pose=None):
-    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "sphere", radius=radius)
+    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "sphere", color=color, radius=radius)
 
 
 def build_red_white_target(scene, radius: float, thickness: float, name: str, body_type: str = "dynamic", add_collision: bool = True, scene_idxs=None, initial_pose=None):
-    """flat disc target (PushCube's goal region); as a collision shape it is one cylinder"""
-    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "cylinder", radius=radius, half_length=thickness / 2)
+    """flat disc target (PushCube's goal region); as a collision shape it is one cylinder, drawn in the red of the
+    reference's outer ring"""
+    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "cylinder", color=(194 / 255, 19 / 255, 22 / 255),
+                            radius=radius, half_length=thickness / 2)
 
 
 def build_twocolor_peg(scene, length, width, color_1, color_2, name: str, body_type="dynamic", add_collision: bool = True, scene_idxs=None, initial_pose=None):
-    return _primitive_actor(scene, name, body_type, add_collision, scene_idxs, initial_pose, "box", half_size=[length, width, width])
+    """one box for the simulation; the shaded view draws its two halves along x in `color_1` (-x) and `color_2` (+x)"""
+    if body_type not in _BUILD_METHOD:
+        raise ValueError(f"Unknown body type {body_type}")
+    builder = scene.create_actor_builder()
+    if add_collision:
+        builder.add_box_collision(half_size=[length, width, width])
+    from maniskill_amd.model import geom
+
+    builder.add_box_visual(pose=geom.pose([-length / 2, 0, 0]), half_size=[length / 2, width, width], material=color_1)
+    builder.add_box_visual(pose=geom.pose([length / 2, 0, 0]), half_size=[length / 2, width, width], material=color_2)
+    if scene_idxs is not None:
+        builder.set_scene_idxs(scene_idxs)
+    if initial_pose is not None:
+        builder.set_initial_pose(initial_pose)
+    return getattr(builder, _BUILD_METHOD[body_type])(name=name)

@@ -1,4 +1,4 @@
-"""ground plane (mani_skill/utils/building/ground.py:18-45); the checker-board visual is dropped"""
+"""ground plane (mani_skill/utils/building/ground.py:18-45); the shaded view of `env.render()` draws it as a 1 m checkered grey board (model/compile.py GROUND_CELL)"""
 import sapien
 
 

@@ -1,5 +1,5 @@
-"""RecordEpisode: trajectory recording in the reference's container layout (counterpart of
-mani_skill/utils/wrappers/record.py:195-760; video recording is out of scope, there is no renderer).
+"""RecordEpisode: trajectory recording in the reference's container layout, and episode videos of `env.render()`
+frames (counterpart of mani_skill/utils/wrappers/record.py:195-760).
 
 On disk, next to each other:
   <name>.json   env_info {env_id, max_episode_steps, env_kwargs}, source_type / source_desc, and per
@@ -11,6 +11,12 @@ On disk, next to each other:
 h5py is not part of this image: without it the same tree is written as <name>.npz with the dataset
 paths as keys ("traj_0/env_states/actors/cube", ...). `maniskill_amd.trajectory.utils.load_h5_data`
 reads either.
+
+With `save_video=True` every reset and step adds one `env.render()` frame (all envs tiled into one picture); a video is
+written at the next full reset, at `flush_video()` / `close()`, or whenever it holds `max_steps_per_video` steps:
+<output_dir>/<video id>.mp4 through imageio, or .png (animated) through PIL where imageio is missing
+(maniskill_amd/utils/visualization/misc.py). The frames are the flat-shaded view of this build, so the env needs a
+working `render_mode` ("rgb_array", "sensors" or "all").
 """
 import json
 import os
@@ -66,10 +72,20 @@ def _np(x):
 class RecordEpisode(gym.Wrapper):
     def __init__(self, env, output_dir: str, save_trajectory: bool = True, trajectory_name: Optional[str] = None, save_on_reset: bool = True,
                  record_reward: bool = True, record_env_state: bool = True, source_type: Optional[str] = None, source_desc: Optional[str] = None,
-                 save_video: bool = False, **_unused):
+                 save_video: bool = False, info_on_video: bool = False, video_fps: int = 30, max_steps_per_video: Optional[int] = None, **_unused):
         super().__init__(env)
+        self.save_video = save_video
+        self.video_fps, self.max_steps_per_video = video_fps, max_steps_per_video
+        self._video_frames, self._video_id, self._video_steps = [], -1, 0
         if save_video:
-            raise NotImplementedError("video recording needs the renderer, which is out of scope of this build")
+            from maniskill_amd.utils.visualization.misc import video_backend
+
+            if info_on_video:
+                raise NotImplementedError("info_on_video draws text on the frames, which this build does not do")
+            mode = getattr(env.unwrapped, "render_mode", None)
+            if mode not in ("rgb_array", "sensors", "all"):
+                raise ValueError(f"save_video=True records env.render() frames: make the env with render_mode=\"rgb_array\", \"sensors\" or \"all\" (it has {mode!r})")
+            video_backend()  # (an ImportError here, not after an episode, where neither imageio nor PIL imports)
         self.output_dir = output_dir
         os.makedirs(output_dir, exist_ok=True)
         self.save_trajectory = save_trajectory
@@ -114,8 +130,32 @@ class RecordEpisode(gym.Wrapper):
         f["success"].append(_np(info["success"]).astype(bool) if info is not None and "success" in info else None)
         f["fail"].append(_np(info["fail"]).astype(bool) if info is not None and "fail" in info else None)
 
+    # ------------------------------------------------------------------ video
+    def capture_image(self) -> np.ndarray:
+        """uint8 [H', W', 3]: env.render() with the envs tiled into one picture (a near-square grid)"""
+        from maniskill_amd.utils.visualization.misc import tile_images
+
+        frames = common.to_numpy(self.env.render())
+        if frames.ndim == 3:
+            return frames
+        rows = int(np.sqrt(len(frames)))
+        return tile_images(list(frames), nrows=rows) if len(frames) > 1 else frames[0]
+
+    def flush_video(self, name: Optional[str] = None, verbose: bool = False, save: bool = True):
+        """writes the collected frames as one video (nothing without frames) and starts the next"""
+        from maniskill_amd.utils.visualization.misc import images_to_video
+
+        path = None
+        if save and len(self._video_frames) > 1:
+            self._video_id += 1
+            path = images_to_video(self._video_frames, self.output_dir, name if name is not None else str(self._video_id), fps=self.video_fps, verbose=verbose)
+        self._video_frames, self._video_steps = [], 0
+        return path
+
     # ------------------------------------------------------------------ gym API
     def reset(self, *args, seed=None, options=None, **kwargs):
+        if self.save_video and self.save_on_reset and (options is None or "env_idx" not in options):
+            self.flush_video()
         if self.save_on_reset and self.save_trajectory and self._frames is not None:
             idx = None
             if options is not None and "env_idx" in options:
@@ -130,6 +170,8 @@ class RecordEpisode(gym.Wrapper):
         self._push(obs, np.zeros((N, adim), np.float32), np.zeros(N, np.float32), np.zeros(N, bool), np.zeros(N, bool), None)
         if options is not None and "env_idx" in options:
             self._ptr[common.to_numpy(options["env_idx"])] = len(self._frames["obs"]) - 1
+        if self.save_video:
+            self._video_frames.append(self.capture_image())
         return obs, info
 
     def step(self, action):
@@ -137,6 +179,11 @@ class RecordEpisode(gym.Wrapper):
         N = self.num_envs
         self._push(obs, _np(action).reshape(N, -1).astype(np.float32), _np(rew).reshape(N).astype(np.float32),
                    _np(terminated).reshape(N).astype(bool), np.broadcast_to(_np(truncated), (N,)).astype(bool), info)
+        if self.save_video:
+            self._video_frames.append(self.capture_image())
+            self._video_steps += 1
+            if self.max_steps_per_video is not None and self._video_steps >= self.max_steps_per_video:
+                self.flush_video()
         return obs, rew, terminated, truncated, info
 
     # ------------------------------------------------------------------ flushing
@@ -204,4 +251,6 @@ class RecordEpisode(gym.Wrapper):
     def close(self):
         if self.save_trajectory and self._frames is not None:
             self.flush_trajectory()
+        if self.save_video:
+            self.flush_video()
         return super().close()
