@@ -7,7 +7,9 @@
 // 6 x 16 B per shape, read back with one address per wave (a broadcast). Every lane then walks the staged list; a
 // shape is skipped by its bounding sphere, by the whole wave when no lane's ray meets the sphere. A hull's planes are
 // read from global memory at addresses that are the same in every lane. No atomics: one lane writes each pixel, with one
-// 8-byte store (and one 4-byte store for the float depth), so a render is deterministic.
+// 8-byte store (and one 4-byte store for the float depth), so a render is deterministic. The shaded view
+// (mssim_raycast_shade.h, k_raycast_shade) stages and walks with the routines of this file -- rc_stage_shape, rc::trace -- and
+// keeps another hit record: what either kernel has in front of a pixel is decided here, once.
 //
 // Triangle meshes (k_raycast<true>, chosen at create for a scene that holds one, or per-env plane ranges or ids, which
 // that instance alone reads while staging; k_raycast<false> is the kernel without any of them, register for register): a staged mesh passes the same bounding-sphere reject, then each lane walks the mesh's 16-wide BVH for its own ray,
@@ -111,16 +113,20 @@ RC_HD Staged stage(xf cam, xf shape, p3 bc_env, float br, int type, const float*
 
 constexpr float kInf = INFINITY;
 
-// the slab |x| <= h along one axis: narrows [*tin, *tout]
-RC_HD void slab(float o, float d, float h, float* tin, float* tout) {
+// the slab |x| <= h along one axis: narrows [*tin, *tout]; true where it raised *tin (strictly: on a tie the earlier slab
+// keeps the entry)
+RC_HD bool slab(float o, float d, float h, float* tin, float* tout) {
   if (d == 0.f) {
     if (fabsf(o) > h) { *tin = kInf; *tout = -kInf; }
-    return;
+    return false;
   }
   const float inv = 1.f / d;
   const float t1 = (-h - o) * inv, t2 = (h - o) * inv;
-  *tin = fmaxf(*tin, fminf(t1, t2));
+  const float lo = fminf(t1, t2);
+  const bool sets = lo > *tin;
+  *tin = fmaxf(*tin, lo);
   *tout = fminf(*tout, fmaxf(t1, t2));
+  return sets;
 }
 
 // the ball of radius r about the origin (`oc`: the ray's start relative to the centre): interval of the line oc + t d
@@ -141,39 +147,47 @@ RC_HD void ball(v3 oc, v3 d, float r, float* tin, float* tout) {
   *tout = tm + half;
 }
 
-// [tin, tout] of a cylinder of radius r and half length h about +x
-RC_HD void cylinder(v3 o, v3 d, float r, float h, float* tin, float* tout) {
+// [tin, tout] of a cylinder of radius r and half length h about +x; *face = 1 where the cap slab set the entry, else 0 (the side)
+RC_HD void cylinder(v3 o, v3 d, float r, float h, float* tin, float* tout, int* face) {
   ball(mk(0.f, o.y, o.z), mk(0.f, d.y, d.z), r, tin, tout);
-  slab(o.x, d.x, h, tin, tout);
+  *face = slab(o.x, d.x, h, tin, tout) ? 1 : 0;
 }
 
 // entry parameter of the ray (o, d) into the shape, in the shape's frame; +inf: the line misses it. An entry < 0 means
-// the start is inside or the shape lies behind: the caller's `near` test drops both.
-RC_HD float enter(int type, const float* p, v3 o, v3 d, const float* __restrict__ planes, int pl0, int pln) {
+// the start is inside or the shape lies behind: the caller's `near` test drops both. *face names the FACE entered, one
+// integer from which the shaded view works out a normal where it needs one (the depth kernel never reads it, and it folds
+// away there):
+//   box 0 / 1 / 2: the axis whose slab set the entry, the lowest on a tie; cylinder 0 side, 1 cap; capsule 0 / 1 its
+//   cylinder's side / cap, 2 the ball at -x, 3 at +x, whichever gave the earliest entry (cylinder first on a tie); hull: the
+//   first plane, by index in its range, that set tin; plane, sphere: 0
+RC_HD float enter(int type, const float* p, v3 o, v3 d, const float* __restrict__ planes, int pl0, int pln, int* face) {
   float tin = -kInf, tout = kInf;
+  *face = 0;
   switch (type) {
     case MSSIM_SHAPE_PLANE:  // solid: x <= 0
       if (!(d.x < 0.f)) return kInf;
       return -o.x / d.x;
     case MSSIM_SHAPE_BOX:
       slab(o.x, d.x, p[0], &tin, &tout);
-      slab(o.y, d.y, p[1], &tin, &tout);
-      slab(o.z, d.z, p[2], &tin, &tout);
+      if (slab(o.y, d.y, p[1], &tin, &tout)) *face = 1;
+      if (slab(o.z, d.z, p[2], &tin, &tout)) *face = 2;
       break;
     case MSSIM_SHAPE_SPHERE:
       ball(o, d, p[0], &tin, &tout);
       break;
     case MSSIM_SHAPE_CYLINDER:
-      cylinder(o, d, p[0], p[1], &tin, &tout);
+      cylinder(o, d, p[0], p[1], &tin, &tout, face);
       break;
     case MSSIM_SHAPE_CAPSULE: {  // the union of a cylinder and two balls, itself convex: the earliest entry of the three
       float best = kInf;
-      cylinder(o, d, p[0], p[1], &tin, &tout);
-      if (tin <= tout) best = tin;
+      int f = 0;
+      cylinder(o, d, p[0], p[1], &tin, &tout, &f);
+      if (tin <= tout) { best = tin; *face = f; }
       for (int k = 0; k < 2; k++) {
         const float cx = k ? p[1] : -p[1];
         ball(mk(o.x - cx, o.y, o.z), d, p[0], &tin, &tout);
-        if (tin <= tout) best = fminf(best, tin);
+        // (fminf(best, tin) but for the sign of a zero, and a zero entry is below every `near`)
+        if (tin <= tout && tin < best) { best = tin; *face = 2 + k; }
       }
       return best;
     }
@@ -187,7 +201,12 @@ RC_HD float enter(int type, const float* p, v3 o, v3 d, const float* __restrict_
           continue;
         }
         const float t = dist / nd;
-        if (nd < 0.f) tin = fmaxf(tin, t); else tout = fminf(tout, t);
+        if (nd < 0.f) {
+          if (t > tin) *face = k;  // (strictly: the first plane in index order keeps the entry)
+          tin = fmaxf(tin, t);
+        } else {
+          tout = fminf(tout, t);
+        }
       }
       break;
     default:
@@ -239,10 +258,11 @@ RC_HD unsigned node_mask(const float* __restrict__ node, v3 o, v3 inv, float lo,
 
 struct MeshLevel { int node; unsigned mask; };  // a level of the walk: the node and its children still to visit
 
-// smallest t in [near, tmax] below `best` over the triangles of the mesh under `root` (shape frame: o, d); `best` where
-// there is none. `stack` holds MSSIM_RAYCAST_MESH_DEPTH levels, `stride` elements apart.
+// smallest t in [near, tmax] below `best` over the triangles of the mesh under `root` (shape frame: o, d); +inf where
+// there is none. *tri = index in `soup` of the triangle that gave the returned t (untouched on a miss). `stack` holds
+// MSSIM_RAYCAST_MESH_DEPTH levels, `stride` elements apart.
 RC_HD float mesh_hit(const float* __restrict__ bvh, const float* __restrict__ soup, int root, v3 o, v3 d, float near, float tmax, float best,
-                     MeshLevel* stack, int stride) {
+                     MeshLevel* stack, int stride, int* tri) {
   const v3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
   best = fminf(best, tmax);
   bool found = false;
@@ -267,7 +287,7 @@ RC_HD float mesh_hit(const float* __restrict__ bvh, const float* __restrict__ so
     if (ref < 0) {
       const float* q = soup + (size_t)(~ref) * 12;
       const float t = triangle(mk(o.x - q[0], o.y - q[1], o.z - q[2]), d, mk(q[3], q[4], q[5]), mk(q[6], q[7], q[8]), mk(q[9], q[10], q[11]));
-      if (t >= near && t <= tmax && (found ? t < best : t <= best)) { best = t; found = true; }
+      if (t >= near && t <= tmax && (found ? t < best : t <= best)) { best = t; found = true; *tri = ~ref; }
       continue;
     }
     if (mask != 0u) {
@@ -281,13 +301,19 @@ RC_HD float mesh_hit(const float* __restrict__ bvh, const float* __restrict__ so
   return found ? best : kInf;
 }
 
-struct Hit { float t; int seg; };
+// the nearest hit so far, as the depth kernel keeps it: parameter and id. A hit record has `t` and take(), which trace
+// calls on an improving hit with all it knows about it (rc::Lit of the shaded view keeps a normal and a colour instead).
+struct Hit {
+  float t; int seg;
+  RC_HD void take(const Staged& s, int, v3, v3, float t_, int, bool, const float*, const float*) { t = t_; seg = s.seg; }
+};
 
-// one pixel's ray (x_cv, y_cv, 1) against staged shapes [0, n): improves `hit` (strictly smaller t only). MESH: a staged
-// TRIMESH shape (pl0 = its root node) is walked through `bvh` / `soup` with the lane's `stack`; without it such a shape is
-// never staged (validate turns a mesh down for a scene without triangle tables, and those choose MESH).
-template <bool MESH>
-RC_HD void trace(const Staged* __restrict__ sh, int n, const float* __restrict__ planes, float xcv, float ycv, float near, float tmax, bool live, Hit* hit,
+// one pixel's ray (x_cv, y_cv, 1) against staged shapes [0, n): improves `hit` (strictly smaller t only) through
+// hit->take(shape, its index in sh, o, d, t, face -- of a mesh: the triangle --, whether it is a mesh, planes, soup). MESH: a
+// staged TRIMESH shape (pl0 = its root node) is walked through `bvh` / `soup` with the lane's `stack`; without it such a
+// shape is never staged (validate turns a mesh down for a scene without triangle tables, and those choose MESH).
+template <bool MESH, class H>
+RC_HD void trace(const Staged* __restrict__ sh, int n, const float* __restrict__ planes, float xcv, float ycv, float near, float tmax, bool live, H* hit,
                  const float* __restrict__ bvh = nullptr, const float* __restrict__ soup = nullptr, MeshLevel* stack = nullptr, int stride = 0) {
   const float dd = xcv * xcv + ycv * ycv + 1.f;
   for (int i = 0; i < n; i++) {
@@ -311,9 +337,11 @@ RC_HD void trace(const Staged* __restrict__ sh, int n, const float* __restrict__
       const v3 o = mk(s.ox, s.oy, s.oz);
       const v3 d = mk(s.r0[0] * xcv + s.r0[1] * ycv + s.r0[2], s.r1[0] * xcv + s.r1[1] * ycv + s.r1[2], s.r2[0] * xcv + s.r2[1] * ycv + s.r2[2]);
       float t;
-      if (MESH && s.type == MSSIM_SHAPE_TRIMESH) t = mesh_hit(bvh, soup, s.pl0, o, d, near, tmax, hit->t, stack, stride);
-      else t = enter(s.type, s.p, o, d, planes, s.pl0, s.pln);
-      if (t >= near && t <= tmax && t < hit->t) { hit->t = t; hit->seg = s.seg; }
+      int face = -1;
+      const bool mesh = MESH && s.type == MSSIM_SHAPE_TRIMESH;
+      if (mesh) t = mesh_hit(bvh, soup, s.pl0, o, d, near, tmax, hit->t, stack, stride, &face);
+      else t = enter(s.type, s.p, o, d, planes, s.pl0, s.pln, &face);
+      if (t >= near && t <= tmax && t < hit->t) hit->take(s, i, o, d, t, face, mesh, planes, soup);
     }
   }
 }
@@ -355,6 +383,59 @@ struct RcObject {
 
 constexpr int RC_TILE = 16;
 
+// the camera in the env frame: its pose, composed with its mount row's (the body row, read here)
+__device__ __forceinline__ rc::xf rc_camera(const RcCamera& C, const float* __restrict__ rigid, int N, int env) {
+  rc::xf cam = C.env_pose ? rc::load_xf(C.env_pose + 7 * (size_t)env, 1) : rc::load_xf(C.pose, 1);
+  if (C.mount_row >= 0) cam = rc::compose(rc::load_xf(rigid + ((size_t)C.mount_row * N + env) * 13, 1), cam);
+  return cam;
+}
+
+// shape i of the scene staged for env `env`: the shared tables, the env's own rows where the shape has a slot (*slot, -1:
+// none), the body row. MESH: the env's own hull and id too (tables that only this variant reads: see RcObject::mesh)
+template <bool MESH>
+__device__ __forceinline__ rc::Staged rc_stage_shape(const RcTables& T, const rc::xf cam, const float* __restrict__ rigid, int N, int env, int i, int* slot_out) {
+  int type = T.type[i];
+  rc::xf frame = rc::load_xf(T.frame + 7 * (size_t)i, 1);
+  float param[3] = {T.param[4 * i], T.param[4 * i + 1], T.param[4 * i + 2]};
+  rc::p3 bc{T.bound[4 * i], T.bound[4 * i + 1], T.bound[4 * i + 2]};
+  float br = T.bound[4 * i + 3];
+  const int slot = T.env_slot ? T.env_slot[i] : -1;
+  if (slot >= 0) {  // [items][N], env fastest
+    frame = rc::load_xf(T.env_frame + (size_t)slot * 7 * N + env, (size_t)N);
+    const float* ep = T.env_param + (size_t)slot * 4 * N + env;
+    const float* eb = T.env_bound + (size_t)slot * 4 * N + env;
+    const int t1 = (int)ep[3 * (size_t)N];
+    if (t1 > 0) type = t1 - 1;
+    if (type != MSSIM_SHAPE_CONVEX && !(MESH && type == MSSIM_SHAPE_TRIMESH && t1 == 0)) { param[0] = ep[0]; param[1] = ep[(size_t)N]; param[2] = ep[2 * (size_t)N]; }
+    bc = rc::p3{eb[0], eb[(size_t)N], eb[2 * (size_t)N]};
+    br = eb[3 * (size_t)N];
+  }
+  const int row = T.row[i];
+  if (row >= 0) {
+    const rc::xf body = rc::load_xf(rigid + ((size_t)row * N + env) * 13, 1);
+    frame = rc::compose(body, frame);
+    bc = body.p + rc::qrot(body.q, bc);
+  }
+  int seg = T.seg[i], pl0 = T.planes2[2 * i], pln = T.planes2[2 * i + 1];
+  if (MESH && slot >= 0) {
+    if (T.env_planes2 && type == MSSIM_SHAPE_CONVEX) { pl0 = T.env_planes2[(size_t)slot * 2 * N + env]; pln = T.env_planes2[((size_t)slot * 2 + 1) * N + env]; }
+    if (T.env_seg) seg = T.env_seg[(size_t)slot * N + env];
+  }
+  if (MESH && type == MSSIM_SHAPE_TRIMESH) { pl0 = (int)param[2]; pln = (int)param[1]; }  // root node, triangle count
+  *slot_out = slot;
+  return rc::stage(cam, frame, bc, br, type, param, seg, pl0, pln);
+}
+
+// which pixel of tile `tile` a lane renders: wave w owns quadrant (w & 1, w >> 1) of the tile, lane l pixel (l & 7, l >> 3)
+// of the quadrant. live: the pixel lies in the image; (xcv, ycv, 1) is its ray.
+struct RcPixel { int u, v; bool live; float xcv, ycv; };
+__device__ __forceinline__ RcPixel rc_pixel(const RcCamera& C, int tiles_x, int tile) {
+  const int tx = tile % tiles_x, ty = tile / tiles_x;
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int u = tx * RC_TILE + (w & 1) * 8 + (l & 7), v = ty * RC_TILE + (w >> 1) * 8 + (l >> 3);
+  return RcPixel{u, v, u < C.width && v < C.height, ((float)u + 0.5f - C.cx) / C.fx, ((float)v + 0.5f - C.cy) / C.fy};
+}
+
 // MESH: the scene holds triangle meshes, per-env hulls or per-env ids (see the head of this file); false is the kernel as
 // it is without them
 template <bool MESH>
@@ -362,62 +443,26 @@ __global__ __launch_bounds__(256) void k_raycast(RcTables T, RcCamera C, const f
                                                  short* __restrict__ pos_seg, float* __restrict__ depth) {
   __shared__ __attribute__((aligned(16))) rc::Staged sh[MSSIM_RAYCAST_CHUNK];
   __shared__ __attribute__((aligned(8))) rc::MeshLevel levels[MESH ? MSSIM_RAYCAST_MESH_DEPTH * 256 : 1];  // [level][lane]
-  const int env = blockIdx.x / tiles, tile = blockIdx.x - env * tiles;
+  const int env = blockIdx.x / tiles;  // block = (env, tile)
   if (env >= N) return;  // (never: the grid is N * tiles)
-  const int tx = tile % tiles_x, ty = tile / tiles_x;
-  // wave w owns quadrant (w & 1, w >> 1) of the tile, lane l pixel (l & 7, l >> 3) of the quadrant
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int u = tx * RC_TILE + (w & 1) * 8 + (l & 7), v = ty * RC_TILE + (w >> 1) * 8 + (l >> 3);
-  const bool live = u < C.width && v < C.height;
-  const float xcv = ((float)u + 0.5f - C.cx) / C.fx, ycv = ((float)v + 0.5f - C.cy) / C.fy;
+  const RcPixel px = rc_pixel(C, tiles_x, blockIdx.x - env * tiles);
   rc::Hit hit{rc::kInf, 0};
 
   for (int base = 0; base < T.n_shape; base += MSSIM_RAYCAST_CHUNK) {
     const int n = min(MSSIM_RAYCAST_CHUNK, T.n_shape - base);
     if (base) __syncthreads();  // the previous chunk has been walked by every wave
     if ((int)threadIdx.x < n) {
-      const int i = base + threadIdx.x;
-      // the camera in the env frame: its mount's pose (the body row, read here) o its local pose
-      rc::xf cam = C.env_pose ? rc::load_xf(C.env_pose + 7 * (size_t)env, 1) : rc::load_xf(C.pose, 1);
-      if (C.mount_row >= 0) cam = rc::compose(rc::load_xf(rigid + ((size_t)C.mount_row * N + env) * 13, 1), cam);
-      int type = T.type[i];
-      rc::xf frame = rc::load_xf(T.frame + 7 * (size_t)i, 1);
-      float param[3] = {T.param[4 * i], T.param[4 * i + 1], T.param[4 * i + 2]};
-      rc::p3 bc{T.bound[4 * i], T.bound[4 * i + 1], T.bound[4 * i + 2]};
-      float br = T.bound[4 * i + 3];
-      const int slot = T.env_slot ? T.env_slot[i] : -1;
-      if (slot >= 0) {  // [items][N], env fastest
-        frame = rc::load_xf(T.env_frame + (size_t)slot * 7 * N + env, (size_t)N);
-        const float* ep = T.env_param + (size_t)slot * 4 * N + env;
-        const float* eb = T.env_bound + (size_t)slot * 4 * N + env;
-        const int t1 = (int)ep[3 * (size_t)N];
-        if (t1 > 0) type = t1 - 1;
-        if (type != MSSIM_SHAPE_CONVEX && !(MESH && type == MSSIM_SHAPE_TRIMESH && t1 == 0)) { param[0] = ep[0]; param[1] = ep[(size_t)N]; param[2] = ep[2 * (size_t)N]; }
-        bc = rc::p3{eb[0], eb[(size_t)N], eb[2 * (size_t)N]};
-        br = eb[3 * (size_t)N];
-      }
-      const int row = T.row[i];
-      if (row >= 0) {
-        const rc::xf body = rc::load_xf(rigid + ((size_t)row * N + env) * 13, 1);
-        frame = rc::compose(body, frame);
-        bc = body.p + rc::qrot(body.q, bc);
-      }
-      int seg = T.seg[i], pl0 = T.planes2[2 * i], pln = T.planes2[2 * i + 1];
-      if (MESH && slot >= 0) {  // the env's own hull and id (tables that only this variant reads: see RcObject::mesh)
-        if (T.env_planes2 && type == MSSIM_SHAPE_CONVEX) { pl0 = T.env_planes2[(size_t)slot * 2 * N + env]; pln = T.env_planes2[((size_t)slot * 2 + 1) * N + env]; }
-        if (T.env_seg) seg = T.env_seg[(size_t)slot * N + env];
-      }
-      if (MESH && type == MSSIM_SHAPE_TRIMESH) { pl0 = (int)param[2]; pln = (int)param[1]; }  // root node, triangle count
-      sh[threadIdx.x] = rc::stage(cam, frame, bc, br, type, param, seg, pl0, pln);
+      int slot;
+      sh[threadIdx.x] = rc_stage_shape<MESH>(T, rc_camera(C, rigid, N, env), rigid, N, env, base + threadIdx.x, &slot);
     }
     __syncthreads();
-    rc::trace<MESH>(sh, n, T.plane, xcv, ycv, C.near, C.tmax, live, &hit, T.tri_bvh, T.tri_soup, levels + (MESH ? threadIdx.x : 0), 256);
+    rc::trace<MESH>(sh, n, T.plane, px.xcv, px.ycv, C.near, C.tmax, px.live, &hit, T.tri_bvh, T.tri_soup, levels + (MESH ? threadIdx.x : 0), 256);
   }
-  if (!live) return;
+  if (!px.live) return;
   const bool any = hit.t < rc::kInf;
   const float t = any ? hit.t : 0.f;
-  const size_t pix = ((size_t)env * C.height + v) * C.width + u;
-  const int x = rc::mm(xcv * t), y = rc::mm(-(ycv * t)), z = rc::mm(-t);
+  const size_t pix = ((size_t)env * C.height + px.v) * C.width + px.u;
+  const int x = rc::mm(px.xcv * t), y = rc::mm(-(px.ycv * t)), z = rc::mm(-t);
   uint2 out;
   out.x = any ? ((unsigned)x & 0xffffu) | ((unsigned)y << 16) : 0u;
   out.y = any ? ((unsigned)z & 0xffffu) | ((unsigned)hit.seg << 16) : 0u;
@@ -432,6 +477,20 @@ static int rc_upload(mssim_handle h, RcObject* o, const Tt* src, size_t count, c
   o->allocs.push_back(d);
   if (count > 0) HIPCHK(h, hipMemcpy(d, src, count * sizeof(Tt), hipMemcpyHostToDevice));
   *dst = (const Tt*)d;
+  return 0;
+}
+
+// what a render or shade call names: the scene, its camera and the camera's tile grid. Refusals carry the caller's name.
+struct RcTarget { const RcObject* o; const RcCamera* C; int tiles_x, tiles; };
+static int rc_target(mssim_handle h, const char* who, int32_t id, int32_t camera, RcTarget* at) {
+  const auto refuse = [&](const char* msg) { h->err = std::string(who) + ": " + msg; return 1; };
+  if (id < 0 || id >= (int)h->raycasts.size() || !h->raycasts[id]) return refuse("bad id");
+  const RcObject& o = *h->raycasts[id];
+  if (camera < 0 || camera >= (int)o.cams.size()) return refuse("bad camera index");
+  if (o.needs_rows && !h->buf.rigid_body_data) return refuse("no rigid_body_data bound");
+  const RcCamera& C = o.cams[camera];
+  const int tiles_x = (C.width + RC_TILE - 1) / RC_TILE;
+  *at = RcTarget{&o, &C, tiles_x, tiles_x * ((C.height + RC_TILE - 1) / RC_TILE)};
   return 0;
 }
 
@@ -504,17 +563,13 @@ int mssim_raycast_destroy(mssim_handle h, int32_t id) {
 int mssim_raycast_render(mssim_handle h, int32_t id, int32_t camera, int16_t* pos_seg, float* depth_f32, void* stream) {
   if (!h) return 1;
   settle(h, (hipStream_t)stream);
-  if (id < 0 || id >= (int)h->raycasts.size() || !h->raycasts[id]) { h->err = "raycast_render: bad id"; return 1; }
-  const RcObject& o = *h->raycasts[id];
-  if (camera < 0 || camera >= (int)o.cams.size()) { h->err = "raycast_render: bad camera index"; return 1; }
+  RcTarget at;
+  if (int rc = rc_target(h, "raycast_render", id, camera, &at)) return rc;
   if (!pos_seg) { h->err = "raycast_render: no pos_seg output"; return 1; }
   if (((uintptr_t)pos_seg & 7u) || ((uintptr_t)depth_f32 & 3u)) { h->err = "raycast_render: pos_seg must be 8-byte aligned, depth_f32 4-byte"; return 1; }
-  if (o.needs_rows && !h->buf.rigid_body_data) { h->err = "raycast_render: no rigid_body_data bound"; return 1; }
-  const RcCamera& C = o.cams[camera];
-  const int tiles_x = (C.width + RC_TILE - 1) / RC_TILE, tiles = tiles_x * ((C.height + RC_TILE - 1) / RC_TILE);
-  const auto kernel = o.mesh ? k_raycast<true> : k_raycast<false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles * h->N)), dim3(256), 0, (hipStream_t)stream, o.T, C, h->buf.rigid_body_data,
-                     h->N, tiles_x, tiles, (short*)pos_seg, depth_f32);
+  const auto kernel = at.o->mesh ? k_raycast<true> : k_raycast<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(at.tiles * h->N)), dim3(256), 0, (hipStream_t)stream, at.o->T, *at.C, h->buf.rigid_body_data,
+                     h->N, at.tiles_x, at.tiles, (short*)pos_seg, depth_f32);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -1,13 +1,17 @@
 // mssim_raycast_shade.h -- the flat-shaded view behind render() and the episode videos (include/mssim_hip_tasks.h,
-// mssim_raycast_set_colours / mssim_raycast_shade). Included by mssim_kernels.hip after mssim_raycast.h, whose staging,
-// bounding-sphere reject, wave-wide skip and BVH walk it reuses; k_raycast itself is not touched.
+// mssim_raycast_set_colours / mssim_raycast_shade). Included by mssim_kernels.hip after mssim_raycast.h. It shows what the
+// depth camera sees by construction: k_raycast_shade stages the shapes with k_raycast's rc_stage_shape and walks them with
+// k_raycast's rc::trace -- one reject, one wave-wide skip, one rc::enter, one BVH walk -- and differs in the hit record alone
+// (rc::Lit here, rc::Hit there).
 //
 // k_raycast_shade has k_raycast's shape: one block per 16 x 16 tile, one lane per pixel, the env's shapes staged in LDS a
 // chunk at a time, beside them one float4 per shape (colour, checker cell) and, once per block, the two light directions
-// in the camera's frame (rotated in double by one lane of wave 1 while wave 0 stages). A later chunk overwrites the staged
-// entries, so a lane whose nearest hit improves works out right then what it will need at the end: the unit normal at the
-// entry point, rotated into the camera frame with the transpose of the staged rows, and the albedo with its checker. What
-// a lane carries across chunks is t, the normal and the albedo: seven registers. One 4-byte store per pixel, no atomics.
+// in the camera's frame (rotated in double by one lane of wave 1 while wave 0 stages). rc::enter and rc::mesh_hit name the
+// FACE a ray entered through, one integer. A later chunk overwrites the staged entries, so a lane whose nearest hit
+// improves works out right then (rc::Lit::take) what it will need at the end: the unit normal at the entry point, from the
+// face (rc::face_normal, rc::triangle_normal), rotated into the camera frame with the transpose of the staged rows, and the
+// albedo with its checker. What a lane carries across chunks is t, the normal and the albedo: seven registers. One 4-byte
+// store per pixel, no atomics.
 //
 // Where a ray enters (shape frame, p = o + t d):
 //   plane     +x (and p.x is taken as exactly 0: the checker must not flicker on the roundings of a point ON the plane)
@@ -42,88 +46,9 @@ constexpr unsigned kBackground = kBackgroundR | (kBackgroundG << 8) | (kBackgrou
 
 RC_HD float against(float d) { return d > 0.f ? -1.f : 1.f; }
 
-// rc::slab, and whether this slab raised *tin (strictly: on a tie the earlier slab keeps the entry)
-RC_HD bool slab_sets(float o, float d, float h, float* tin, float* tout) {
-  if (d == 0.f) {
-    if (fabsf(o) > h) { *tin = kInf; *tout = -kInf; }
-    return false;
-  }
-  const float inv = 1.f / d;
-  const float t1 = (-h - o) * inv, t2 = (h - o) * inv;
-  const float lo = fminf(t1, t2);
-  const bool sets = lo > *tin;
-  *tin = fmaxf(*tin, lo);
-  *tout = fminf(*tout, fmaxf(t1, t2));
-  return sets;
-}
-
 RC_HD v3 unit(v3 a) { return (1.f / sqrtf(dot(a, a))) * a; }
 
-// The walk asks every staged shape for its entry, but needs a normal only where the hit improves: rc::enter_face is
-// rc::enter (the same entry parameter, operation for operation) that also names the FACE entered, one integer, and
-// rc::face_normal works the normal out from it afterwards.
-//   box 0 / 1 / 2: the axis; cylinder 0 side, 1 cap; capsule 0 / 1 its cylinder's side / cap, 2 the ball at -x, 3 at +x;
-//   hull: the plane's index in its range; plane, sphere: 0
-RC_HD void cylinder_face(v3 o, v3 d, float r, float h, float* tin, float* tout, int* face) {
-  ball(mk(0.f, o.y, o.z), mk(0.f, d.y, d.z), r, tin, tout);
-  *face = slab_sets(o.x, d.x, h, tin, tout) ? 1 : 0;
-}
-
-RC_HD float enter_face(int type, const float* p, v3 o, v3 d, const float* __restrict__ planes, int pl0, int pln, int* face) {
-  float tin = -kInf, tout = kInf;
-  *face = 0;
-  switch (type) {
-    case MSSIM_SHAPE_PLANE:
-      if (!(d.x < 0.f)) return kInf;
-      return -o.x / d.x;
-    case MSSIM_SHAPE_BOX:
-      slab_sets(o.x, d.x, p[0], &tin, &tout);
-      if (slab_sets(o.y, d.y, p[1], &tin, &tout)) *face = 1;
-      if (slab_sets(o.z, d.z, p[2], &tin, &tout)) *face = 2;
-      break;
-    case MSSIM_SHAPE_SPHERE:
-      ball(o, d, p[0], &tin, &tout);
-      break;
-    case MSSIM_SHAPE_CYLINDER:
-      cylinder_face(o, d, p[0], p[1], &tin, &tout, face);
-      break;
-    case MSSIM_SHAPE_CAPSULE: {
-      float best = kInf;
-      int f = 0;
-      cylinder_face(o, d, p[0], p[1], &tin, &tout, &f);
-      if (tin <= tout) { best = tin; *face = f; }
-      for (int k = 0; k < 2; k++) {
-        const float cx = k ? p[1] : -p[1];
-        ball(mk(o.x - cx, o.y, o.z), d, p[0], &tin, &tout);
-        if (tin <= tout && tin < best) { best = tin; *face = 2 + k; }
-      }
-      return best;
-    }
-    case MSSIM_SHAPE_CONVEX:
-      for (int k = 0; k < pln; k++) {
-        const float* pl = planes + 4 * (size_t)(pl0 + k);
-        const v3 m = mk(pl[0], pl[1], pl[2]);
-        const float nd = dot(m, d), dist = pl[3] - dot(m, o);
-        if (nd == 0.f) {
-          if (dist < 0.f) return kInf;
-          continue;
-        }
-        const float t = dist / nd;
-        if (nd < 0.f) {
-          if (t > tin) *face = k;  // (strictly: the first plane in index order keeps the entry)
-          tin = fmaxf(tin, t);
-        } else {
-          tout = fminf(tout, t);
-        }
-      }
-      break;
-    default:
-      return kInf;
-  }
-  return tin <= tout ? tin : kInf;
-}
-
-// outward unit normal (shape frame) where the ray o + t d enters the shape through `face`, t and face from rc::enter_face
+// outward unit normal (shape frame) where the ray o + t d enters the shape through `face`, t and face from rc::enter
 RC_HD v3 face_normal(int type, const float* p, v3 o, v3 d, float t, int face, const float* __restrict__ planes, int pl0) {
   switch (type) {
     case MSSIM_SHAPE_BOX:
@@ -149,50 +74,9 @@ RC_HD v3 face_normal(int type, const float* p, v3 o, v3 d, float t, int face, co
 // entry parameter and normal in one call (what tests/native/shade_check.cpp pins); *n is untouched where the line misses
 RC_HD float enter_normal(int type, const float* p, v3 o, v3 d, const float* __restrict__ planes, int pl0, int pln, v3* n) {
   int face;
-  const float t = enter_face(type, p, o, d, planes, pl0, pln, &face);
+  const float t = enter(type, p, o, d, planes, pl0, pln, &face);
   if (t < kInf) *n = face_normal(type, p, o, d, t, face, planes, pl0);
   return t;
-}
-
-// rc::mesh_hit that also names the triangle: *tri = index in `soup` of the one that gave the returned t (untouched on a miss)
-RC_HD float mesh_hit_tri(const float* __restrict__ bvh, const float* __restrict__ soup, int root, v3 o, v3 d, float near, float tmax, float best,
-                         MeshLevel* stack, int stride, int* tri) {
-  const v3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
-  best = fminf(best, tmax);
-  bool found = false;
-  int sp = 0, node = root;
-  unsigned mask = node_mask(bvh + (size_t)node * 112, o, inv, near, best);
-  for (;;) {
-    if (mask == 0u) {
-      if (sp == 0) break;
-      sp--;
-      node = stack[sp * stride].node; mask = stack[sp * stride].mask;
-      continue;
-    }
-    const int c = __builtin_ctz(mask);
-    mask &= mask - 1u;
-    const float* nd = bvh + (size_t)node * 112;
-    int ref;
-#ifdef __HIP_DEVICE_COMPILE__
-    ref = __float_as_int(nd[96 + c]);
-#else
-    memcpy(&ref, nd + 96 + c, 4);
-#endif
-    if (ref < 0) {
-      const float* q = soup + (size_t)(~ref) * 12;
-      const float t = triangle(mk(o.x - q[0], o.y - q[1], o.z - q[2]), d, mk(q[3], q[4], q[5]), mk(q[6], q[7], q[8]), mk(q[9], q[10], q[11]));
-      if (t >= near && t <= tmax && (found ? t < best : t <= best)) { best = t; found = true; *tri = ~ref; }
-      continue;
-    }
-    if (mask != 0u) {
-      if (sp == MSSIM_RAYCAST_MESH_DEPTH) continue;  // (never: validate bounds the depth)
-      stack[sp * stride].node = node; stack[sp * stride].mask = mask;
-      sp++;
-    }
-    node = ref;
-    mask = node_mask(bvh + (size_t)node * 112, o, inv, near, best);
-  }
-  return found ? best : kInf;
 }
 
 // unit normal of triangle `tri` of the soup, turned against the ray's direction d
@@ -232,47 +116,20 @@ RC_HD unsigned shade(v3 n, v3 a, const float* L) {
   return channel(a.x * k) | (channel(a.y * k) << 8) | (channel(a.z * k) << 16) | 0xff000000u;
 }
 
-struct Lit { float t; v3 n, a; };  // the nearest hit so far: parameter, unit normal in the camera frame, albedo
-
-// rc::trace for the shaded view: `col` holds four floats per staged shape. Improves `hit` (strictly smaller t only), and
-// with it the normal and the albedo, which a later chunk could no longer work out.
-template <bool MESH>
-RC_HD void trace_shade(const Staged* __restrict__ sh, const float* __restrict__ col, int n, const float* __restrict__ planes, float xcv, float ycv, float near,
-                       float tmax, bool live, Lit* hit, const float* __restrict__ bvh = nullptr, const float* __restrict__ soup = nullptr,
-                       MeshLevel* stack = nullptr, int stride = 0) {
-  const float dd = xcv * xcv + ycv * ycv + 1.f;
-  for (int i = 0; i < n; i++) {
-    const Staged& s = sh[i];
-    if (s.type == MSSIM_SHAPE_NONE) continue;
-    bool need = live;
-    if (s.br >= 0.f) {  // the reject of rc::trace, with its margins
-      const float cd = s.bc[0] * xcv + s.bc[1] * ycv + s.bc[2];
-      const float cc = s.bc[0] * s.bc[0] + s.bc[1] * s.bc[1] + s.bc[2] * s.bc[2];
-      const float r = 1.01f * s.br + 1e-3f;
-      need = need && (cc * dd - cd * cd <= (r * r + 2e-6f * cc) * dd);
-    }
-#ifdef __HIP_DEVICE_COMPILE__
-    if (__ballot(need) == 0ull) continue;  // the whole wave skips the shape
-#endif
-    if (need) {
-      const v3 o = mk(s.ox, s.oy, s.oz);
-      const v3 d = mk(s.r0[0] * xcv + s.r0[1] * ycv + s.r0[2], s.r1[0] * xcv + s.r1[1] * ycv + s.r1[2], s.r2[0] * xcv + s.r2[1] * ycv + s.r2[2]);
-      float t;
-      int face = -1;  // (of a mesh: the triangle)
-      const bool mesh = MESH && s.type == MSSIM_SHAPE_TRIMESH;
-      if (mesh) t = mesh_hit_tri(bvh, soup, s.pl0, o, d, near, tmax, hit->t, stack, stride, &face);
-      else t = enter_face(s.type, s.p, o, d, planes, s.pl0, s.pln, &face);
-      if (t >= near && t <= tmax && t < hit->t) {
-        const v3 ns = mesh ? triangle_normal(soup, face, d) : face_normal(s.type, s.p, o, d, t, face, planes, s.pl0);
-        hit->t = t;
-        // p_shape = R p_cv: a shape-frame direction goes back with the transpose
-        hit->n = mk(s.r0[0] * ns.x + s.r1[0] * ns.y + s.r2[0] * ns.z, s.r0[1] * ns.x + s.r1[1] * ns.y + s.r2[1] * ns.z,
-                    s.r0[2] * ns.x + s.r1[2] * ns.y + s.r2[2] * ns.z);
-        hit->a = albedo(col + 4 * i, o + t * d, s.type);
-      }
-    }
+// the nearest hit so far as the shaded view keeps it (rc::Hit's counterpart for rc::trace): parameter, unit normal in the
+// camera frame, albedo -- a later chunk could no longer work the last two out. `col` holds four floats per shape of the
+// staged chunk being walked.
+struct Lit {
+  float t; v3 n, a; const float* col;
+  RC_HD void take(const Staged& s, int i, v3 o, v3 d, float t_, int face, bool mesh, const float* __restrict__ planes, const float* __restrict__ soup) {
+    const v3 ns = mesh ? triangle_normal(soup, face, d) : face_normal(s.type, s.p, o, d, t_, face, planes, s.pl0);
+    t = t_;
+    // p_shape = R p_cv: a shape-frame direction goes back with the transpose
+    n = mk(s.r0[0] * ns.x + s.r1[0] * ns.y + s.r2[0] * ns.z, s.r0[1] * ns.x + s.r1[1] * ns.y + s.r2[1] * ns.z,
+           s.r0[2] * ns.x + s.r1[2] * ns.y + s.r2[2] * ns.z);
+    a = albedo(col + 4 * i, o + t_ * d, s.type);
   }
-}
+};
 
 }  // namespace rc
 
@@ -318,38 +175,6 @@ inline int validate_shade(bool have_colours, const void* rgba_u8, std::string* e
 
 #ifdef __HIPCC__
 
-// one shape of the scene staged for env `env` as k_raycast stages it (the same reads and the same double arithmetic)
-template <bool MESH>
-__device__ __forceinline__ rc::Staged rc_stage_shape(const RcTables& T, const rc::xf cam, const float* __restrict__ rigid, int N, int env, int i, int* slot_out) {
-  int type = T.type[i];
-  rc::xf frame = rc::load_xf(T.frame + 7 * (size_t)i, 1);
-  float param[3] = {T.param[4 * i], T.param[4 * i + 1], T.param[4 * i + 2]};
-  rc::p3 bc{T.bound[4 * i], T.bound[4 * i + 1], T.bound[4 * i + 2]};
-  float br = T.bound[4 * i + 3];
-  const int slot = T.env_slot ? T.env_slot[i] : -1;
-  if (slot >= 0) {  // [items][N], env fastest
-    frame = rc::load_xf(T.env_frame + (size_t)slot * 7 * N + env, (size_t)N);
-    const float* ep = T.env_param + (size_t)slot * 4 * N + env;
-    const float* eb = T.env_bound + (size_t)slot * 4 * N + env;
-    const int t1 = (int)ep[3 * (size_t)N];
-    if (t1 > 0) type = t1 - 1;
-    if (type != MSSIM_SHAPE_CONVEX && !(MESH && type == MSSIM_SHAPE_TRIMESH && t1 == 0)) { param[0] = ep[0]; param[1] = ep[(size_t)N]; param[2] = ep[2 * (size_t)N]; }
-    bc = rc::p3{eb[0], eb[(size_t)N], eb[2 * (size_t)N]};
-    br = eb[3 * (size_t)N];
-  }
-  const int row = T.row[i];
-  if (row >= 0) {
-    const rc::xf body = rc::load_xf(rigid + ((size_t)row * N + env) * 13, 1);
-    frame = rc::compose(body, frame);
-    bc = body.p + rc::qrot(body.q, bc);
-  }
-  int pl0 = T.planes2[2 * i], pln = T.planes2[2 * i + 1];
-  if (MESH && slot >= 0 && T.env_planes2 && type == MSSIM_SHAPE_CONVEX) { pl0 = T.env_planes2[(size_t)slot * 2 * N + env]; pln = T.env_planes2[((size_t)slot * 2 + 1) * N + env]; }
-  if (MESH && type == MSSIM_SHAPE_TRIMESH) { pl0 = (int)param[2]; pln = (int)param[1]; }  // root node, triangle count
-  *slot_out = slot;
-  return rc::stage(cam, frame, bc, br, type, param, 0, pl0, pln);
-}
-
 // MESH as in k_raycast; it is also the variant that reads the per-env colours. rgba: [n_shape] float4, env_rgba:
 // [slots][N] float4, env fastest (null: the shared colour in every env). out: [N][H][W] r | g << 8 | b << 16 | 255 << 24.
 template <bool MESH>
@@ -359,22 +184,17 @@ __global__ __launch_bounds__(256) void k_raycast_shade(RcTables T, RcCamera C, c
   __shared__ __attribute__((aligned(16))) float col[4 * MSSIM_RAYCAST_CHUNK];
   __shared__ float light[6];
   __shared__ __attribute__((aligned(8))) rc::MeshLevel levels[MESH ? MSSIM_RAYCAST_MESH_DEPTH * 256 : 1];  // [level][lane]
-  const int env = blockIdx.x / tiles, tile = blockIdx.x - env * tiles;
+  const int env = blockIdx.x / tiles;  // block = (env, tile)
   if (env >= N) return;  // (never: the grid is N * tiles)
-  const int tx = tile % tiles_x, ty = tile / tiles_x;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int u = tx * RC_TILE + (w & 1) * 8 + (l & 7), v = ty * RC_TILE + (w >> 1) * 8 + (l >> 3);
-  const bool live = u < C.width && v < C.height;
-  const float xcv = ((float)u + 0.5f - C.cx) / C.fx, ycv = ((float)v + 0.5f - C.cy) / C.fy;
-  rc::Lit hit{rc::kInf, rc::mk(0.f, 0.f, 0.f), rc::mk(0.f, 0.f, 0.f)};
+  const RcPixel px = rc_pixel(C, tiles_x, blockIdx.x - env * tiles);
+  rc::Lit hit{rc::kInf, rc::mk(0.f, 0.f, 0.f), rc::mk(0.f, 0.f, 0.f), col};
 
   for (int base = 0; base < T.n_shape; base += MSSIM_RAYCAST_CHUNK) {
     const int n = min(MSSIM_RAYCAST_CHUNK, T.n_shape - base);
     if (base) __syncthreads();  // the previous chunk has been walked by every wave
     const bool stages = (int)threadIdx.x < n, lights = base == 0 && threadIdx.x == 64;
     if (stages || lights) {
-      rc::xf cam = C.env_pose ? rc::load_xf(C.env_pose + 7 * (size_t)env, 1) : rc::load_xf(C.pose, 1);
-      if (C.mount_row >= 0) cam = rc::compose(rc::load_xf(rigid + ((size_t)C.mount_row * N + env) * 13, 1), cam);
+      const rc::xf cam = rc_camera(C, rigid, N, env);
       if (lights) {
         rc::lights(cam, light);
       } else {
@@ -387,10 +207,10 @@ __global__ __launch_bounds__(256) void k_raycast_shade(RcTables T, RcCamera C, c
       }
     }
     __syncthreads();
-    rc::trace_shade<MESH>(sh, col, n, T.plane, xcv, ycv, C.near, C.tmax, live, &hit, T.tri_bvh, T.tri_soup, levels + (MESH ? threadIdx.x : 0), 256);
+    rc::trace<MESH>(sh, n, T.plane, px.xcv, px.ycv, C.near, C.tmax, px.live, &hit, T.tri_bvh, T.tri_soup, levels + (MESH ? threadIdx.x : 0), 256);
   }
-  if (!live) return;
-  out[((size_t)env * C.height + v) * C.width + u] = hit.t < rc::kInf ? rc::shade(hit.n, hit.a, light) : rc::kBackground;
+  if (!px.live) return;
+  out[((size_t)env * C.height + px.v) * C.width + px.u] = hit.t < rc::kInf ? rc::shade(hit.n, hit.a, light) : rc::kBackground;
 }
 
 extern "C" {
@@ -419,16 +239,13 @@ int mssim_raycast_set_colours(mssim_handle h, int32_t id, const float* shape_rgb
 int mssim_raycast_shade(mssim_handle h, int32_t id, int32_t camera, uint8_t* rgba_u8, void* stream) {
   if (!h) return 1;
   settle(h, (hipStream_t)stream);
-  if (id < 0 || id >= (int)h->raycasts.size() || !h->raycasts[id]) { h->err = "raycast_shade: bad id"; return 1; }
-  const RcObject& o = *h->raycasts[id];
-  if (camera < 0 || camera >= (int)o.cams.size()) { h->err = "raycast_shade: bad camera index"; return 1; }
+  RcTarget at;
+  if (int rc = rc_target(h, "raycast_shade", id, camera, &at)) return rc;
+  const RcObject& o = *at.o;
   if (int rc = mssim_shade::validate_shade(o.rgba != nullptr, rgba_u8, &h->err)) return rc;
-  if (o.needs_rows && !h->buf.rigid_body_data) { h->err = "raycast_shade: no rigid_body_data bound"; return 1; }
-  const RcCamera& C = o.cams[camera];
-  const int tiles_x = (C.width + RC_TILE - 1) / RC_TILE, tiles = tiles_x * ((C.height + RC_TILE - 1) / RC_TILE);
   const auto kernel = (o.mesh || o.env_rgba) ? k_raycast_shade<true> : k_raycast_shade<false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles * h->N)), dim3(256), 0, (hipStream_t)stream, o.T, C, h->buf.rigid_body_data,
-                     (const float4*)o.rgba, (const float4*)o.env_rgba, h->N, tiles_x, tiles, (unsigned*)rgba_u8);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(at.tiles * h->N)), dim3(256), 0, (hipStream_t)stream, o.T, *at.C, h->buf.rigid_body_data,
+                     (const float4*)o.rgba, (const float4*)o.env_rgba, h->N, at.tiles_x, at.tiles, (unsigned*)rgba_u8);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -1,9 +1,11 @@
 // shade_check.cpp -- CPU check of maniskill_amd/csrc/mssim_raycast_shade.h: the normal, albedo and light routines of the
 // flat-shaded view (namespace rc, the code k_raycast_shade runs per pixel) on a table of rays with closed-form answers,
-// and what mssim_raycast_set_colours / mssim_raycast_shade refuse (namespace mssim_shade), with every table exactly as
-// long as its counts say. Stand-alone (tests/test_shade.py builds it with ASan + UBSan and expects exit status 0).
+// the one walk (rc::trace) into the depth kernel's hit record and into the shaded view's, ray for ray, and what
+// mssim_raycast_set_colours / mssim_raycast_shade refuse (namespace mssim_shade), with every table exactly as long as its
+// counts say. Stand-alone (tests/test_shade.py builds it with ASan + UBSan and expects exit status 0).
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
@@ -34,8 +36,6 @@ Entry enter(int type, std::vector<float> p, v3 o, v3 d, const std::vector<float>
   p.resize(3);
   Entry e{0.f, mk(9.f, 9.f, 9.f)};
   e.t = rc::enter_normal(type, p.data(), o, d, planes.data(), 0, (int)(planes.size() / 4), &e.n);
-  // the entry parameter is rc::enter's, bit for bit: the shaded view and the depth image agree on what is in front
-  CHECK(e.t == rc::enter(type, p.data(), o, d, planes.data(), 0, (int)(planes.size() / 4)));
   return e;
 }
 
@@ -96,27 +96,32 @@ void normals() {
   CHECK(close(e.t, 1.5f) && close3(e.n, 0, 0, 1));
 }
 
-void triangles() {
-  // one triangle in the plane z = 0.25 about its centroid, one BVH node whose child 0 is that leaf: seen from above and
-  // from below it turns its normal to the ray
+// one triangle in the plane z = 0.25 about its centroid, and one BVH node whose child 0 is that leaf
+struct OneTriangle {
   const float soup[12] = {0.f, 0.f, 0.25f, 1.f, -0.5f, 0.f, -0.5f, 1.f, 0.f, -0.5f, -0.5f, 0.f};
-  std::vector<float> node(112, 0.f);
-  for (int c = 0; c < 16; c++) { node[6 * c] = 1.f; node[6 * c + 3] = -1.f; }  // min > max: no child
-  const float box[6] = {-0.5f, -0.5f, 0.25f, 1.f, 1.f, 0.25f};
-  for (int k = 0; k < 6; k++) node[k] = box[k];
-  const int32_t leaf = ~0;
-  std::memcpy(&node[96], &leaf, 4);
+  std::vector<float> node = std::vector<float>(112, 0.f);
+  OneTriangle() {
+    for (int c = 0; c < 16; c++) { node[6 * c] = 1.f; node[6 * c + 3] = -1.f; }  // min > max: no child
+    const float box[6] = {-0.5f, -0.5f, 0.25f, 1.f, 1.f, 0.25f};
+    for (int k = 0; k < 6; k++) node[k] = box[k];
+    const int32_t leaf = ~0;
+    std::memcpy(&node[96], &leaf, 4);
+  }
+};
+
+void triangles() {
+  // seen from above and from below the triangle turns its normal to the ray
+  const OneTriangle m;
   rc::MeshLevel stack[MSSIM_RAYCAST_MESH_DEPTH];
   for (int s = -1; s <= 1; s += 2) {
     const v3 o = mk(0.1f, 0.1f, 0.25f + 2.f * s), d = mk(0, 0, -1.f * s);
     int tri = -1;
-    const float t = rc::mesh_hit_tri(node.data(), soup, 0, o, d, 0.01f, 30.f, rc::kInf, stack, 1, &tri);
+    const float t = rc::mesh_hit(m.node.data(), m.soup, 0, o, d, 0.01f, 30.f, rc::kInf, stack, 1, &tri);
     CHECK(close(t, 2.f) && tri == 0);
-    CHECK(t == rc::mesh_hit(node.data(), soup, 0, o, d, 0.01f, 30.f, rc::kInf, stack, 1));
-    CHECK(close3(rc::triangle_normal(soup, tri, d), 0, 0, (float)s));
+    CHECK(close3(rc::triangle_normal(m.soup, tri, d), 0, 0, (float)s));
   }
   int tri = -7;
-  CHECK(std::isinf(rc::mesh_hit_tri(node.data(), soup, 0, mk(3, 3, 2), mk(0, 0, -1), 0.01f, 30.f, rc::kInf, stack, 1, &tri)) && tri == -7);
+  CHECK(std::isinf(rc::mesh_hit(m.node.data(), m.soup, 0, mk(3, 3, 2), mk(0, 0, -1), 0.01f, 30.f, rc::kInf, stack, 1, &tri)) && tri == -7);
 }
 
 void light_and_colour() {
@@ -155,8 +160,8 @@ void light_and_colour() {
   CHECK(byte_of(rc::kBackground, 3) == 255u);
 }
 
-// trace_shade over a staged list on the host: a hit in the first of two calls keeps its normal and colour while a second
-// list (the next chunk) is walked, and a nearer shape of the second list replaces all three
+// rc::trace into a Lit over a staged list on the host: a hit in the first of two calls keeps its normal and colour while a
+// second list (the next chunk) is walked, and a nearer shape of the second list replaces all three
 void trace() {
   const rc::xf cam{rc::p3{0, 0, 0}, rc::q4{1, 0, 0, 0}};  // looks along env +x
   const float r[3] = {0.5f, 0, 0};
@@ -164,15 +169,76 @@ void trace() {
   const rc::Staged near_ball = rc::stage(cam, rc::xf{rc::p3{3, 0, 0}, rc::q4{1, 0, 0, 0}}, rc::p3{3, 0, 0}, 0.5f, MSSIM_SHAPE_SPHERE, r, 0, 0, 0);
   const rc::Staged off_ball = rc::stage(cam, rc::xf{rc::p3{3, 4, 0}, rc::q4{1, 0, 0, 0}}, rc::p3{3, 4, 0}, 0.5f, MSSIM_SHAPE_SPHERE, r, 0, 0, 0);
   const float red[4] = {1, 0, 0, 0}, green[4] = {0, 1, 0, 0};
-  rc::Lit hit{rc::kInf, mk(0, 0, 0), mk(0, 0, 0)};
-  rc::trace_shade<false>(&far_ball, red, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);
+  rc::Lit hit{rc::kInf, mk(0, 0, 0), mk(0, 0, 0), red};
+  rc::trace<false>(&far_ball, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);
   CHECK(close(hit.t, 4.5f) && close3(hit.n, 0, 0, -1) && hit.a.x == 1.f && hit.a.y == 0.f);
-  rc::trace_shade<false>(&off_ball, green, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);  // missed: everything kept
+  hit.col = green;
+  rc::trace<false>(&off_ball, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);  // missed: everything kept
   CHECK(close(hit.t, 4.5f) && close3(hit.n, 0, 0, -1) && hit.a.x == 1.f && hit.a.y == 0.f);
-  rc::trace_shade<false>(&near_ball, green, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);
+  rc::trace<false>(&near_ball, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);
   CHECK(close(hit.t, 2.5f) && close3(hit.n, 0, 0, -1) && hit.a.x == 0.f && hit.a.y == 1.f);
-  rc::trace_shade<false>(&far_ball, red, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);  // farther: everything kept
+  hit.col = red;
+  rc::trace<false>(&far_ball, 1, nullptr, 0.f, 0.f, 0.01f, 30.f, true, &hit);  // farther: everything kept
   CHECK(close(hit.t, 2.5f) && hit.a.y == 1.f);
+}
+
+// The shaded view and the depth image agree on what is in front, bit for bit: one staged list walked twice by rc::trace,
+// once into the depth kernel's record and once into the shaded view's, over a grid of rays. Returns how many rays hit
+// each id (index 0: nothing).
+template <bool MESH>
+std::vector<int> walk_twice(const std::vector<rc::Staged>& list, const std::vector<float>& planes, const float* bvh, const float* soup) {
+  const int n = (int)list.size();
+  const std::vector<float> col(4 * list.size(), 0.5f);
+  std::vector<int> seen(list.size() + 1, 0);
+  rc::MeshLevel stack[MSSIM_RAYCAST_MESH_DEPTH];
+  for (int v = 0; v < 41; v++)
+    for (int u = 0; u < 41; u++) {
+      const float xcv = 0.3f * (u - 20) / 20.f, ycv = 0.3f * (v - 20) / 20.f;
+      rc::Hit hit{rc::kInf, 0};
+      rc::Lit lit{rc::kInf, mk(0, 0, 0), mk(0, 0, 0), col.data()};
+      rc::trace<MESH>(list.data(), n, planes.data(), xcv, ycv, 0.01f, 30.f, true, &hit, bvh, soup, stack, 1);
+      rc::trace<MESH>(list.data(), n, planes.data(), xcv, ycv, 0.01f, 30.f, true, &lit, bvh, soup, stack, 1);
+      CHECK(std::memcmp(&hit.t, &lit.t, 4) == 0);
+      CHECK(std::isinf(hit.t) || close(rc::dot(lit.n, lit.n), 1.f, 1e-5f));
+      seen[hit.seg]++;
+    }
+  return seen;
+}
+
+void one_walk() {
+  const rc::xf cam{rc::p3{0, 0, 0}, rc::q4{1, 0, 0, 0}};  // looks along env +x
+  auto at = [&](double x, double y, double z, rc::q4 q) { return rc::xf{rc::p3{x, y, z}, rc::qnorm(q)}; };
+  auto staged = [&](rc::xf pose, float br, int type, std::vector<float> p, int seg, int pl0 = 0, int pln = 0) {
+    p.resize(3);
+    return rc::stage(cam, pose, pose.p, br, type, p.data(), seg, pl0, pln);
+  };
+  // a box, a capsule, a hull (a box's six planes) and a sphere, all tilted; the sphere stands in front of part of the box
+  const std::vector<float> planes = {1, 0, 0, 0.3f, -1, 0, 0, 0.3f, 0, 1, 0, 0.2f, 0, -1, 0, 0.2f, 0, 0, 1, 0.1f, 0, 0, -1, 0.1f};
+  const std::vector<rc::Staged> list = {
+      staged(at(4.0, 0.6, 0.3, {0.9, 0.1, -0.3, 0.2}), 0.45f, MSSIM_SHAPE_BOX, {0.3f, 0.2f, 0.25f}, 1),
+      staged(at(3.0, -0.5, -0.2, {0.8, -0.2, 0.4, 0.3}), 0.55f, MSSIM_SHAPE_CAPSULE, {0.15f, 0.4f}, 2),
+      staged(at(5.0, 0.1, -0.6, {0.7, 0.5, 0.1, -0.4}), 0.38f, MSSIM_SHAPE_CONVEX, {}, 3, 0, 6),
+      staged(at(3.5, 0.3, 0.25, {1, 0, 0, 0}), 0.2f, MSSIM_SHAPE_SPHERE, {0.2f}, 4),
+  };
+  const std::vector<int> seen = walk_twice<false>(list, planes, nullptr, nullptr);
+  for (int k = 0; k <= 4; k++) CHECK(seen[k] > 10);  // every shape and the background are in the picture
+  // the ray at the sphere's centre enters it at z-depth 3.5 (1 - r / |c|); the ray at the box's centre passes beside the
+  // sphere; a ray between the two meets both, and the sphere is in front
+  rc::Hit centre{rc::kInf, 0}, beside{rc::kInf, 0}, both{rc::kInf, 0}, box_alone{rc::kInf, 0};
+  rc::trace<false>(list.data(), 4, planes.data(), -0.3f / 3.5f, -0.25f / 3.5f, 0.01f, 30.f, true, &centre);
+  rc::trace<false>(list.data(), 4, planes.data(), -0.6f / 4.f, -0.3f / 4.f, 0.01f, 30.f, true, &beside);
+  rc::trace<false>(list.data(), 4, planes.data(), -0.12f, -0.073f, 0.01f, 30.f, true, &both);
+  rc::trace<false>(list.data(), 1, planes.data(), -0.12f, -0.073f, 0.01f, 30.f, true, &box_alone);
+  CHECK(centre.seg == 4 && close(centre.t, 3.5f * (1.f - 0.2f / std::sqrt(12.4025f)), 1e-5f) && beside.seg == 1);
+  CHECK(both.seg == 4 && box_alone.seg == 1 && both.t < box_alone.t && box_alone.t < 30.f);
+  // the one-triangle mesh, turned to face the camera (its z along env -x), and a sphere in front of its middle
+  const OneTriangle m;
+  const std::vector<rc::Staged> with_mesh = {
+      staged(at(4.0, 0.0, 0.0, {0.7071067811865476, 0, -0.7071067811865476, 0}), 2.f, MSSIM_SHAPE_TRIMESH, {}, 1, 0, 1),
+      staged(at(3.0, 0.1, 0.1, {1, 0, 0, 0}), 0.2f, MSSIM_SHAPE_SPHERE, {0.2f}, 2),
+  };
+  const std::vector<int> seen_mesh = walk_twice<true>(with_mesh, {}, m.node.data(), m.soup);
+  for (int k = 0; k <= 2; k++) CHECK(seen_mesh[k] > 10);
 }
 
 void refusals() {
@@ -211,6 +277,7 @@ int main() {
   triangles();
   light_and_colour();
   trace();
+  one_walk();
   refusals();
   if (g_failed) {
     std::printf("shade_check: %d checks failed\n", g_failed);

@@ -6,7 +6,9 @@ On the pixels the reference does not call ambiguous every channel is within ONE 
 measured: a unit normal and two dot products in float32 are some 1e-6 of full scale off, far below one level, so the
 rounding to a byte can move by at most one. Alpha is 255 everywhere, pixels the reference calls empty carry the background
 colour exactly, GUARD bytes behind the last pixel stay as they were, no pixel is left unwritten, a second launch repeats
-the first bit for bit, and a depth render of the same scene before and after the shading launch is bit-identical."""
+the first bit for bit, and a depth render of the same scene before and after the shading launch is bit-identical. The
+picture and the depth image come from one walk of the shapes, so on EVERY pixel, the ambiguous ones included, the
+background colour stands exactly where the float depth is 0."""
 import numpy as np
 import pytest
 import torch
@@ -45,9 +47,21 @@ def compare(what, rgba, per_env):
     return worst
 
 
+def can_shade_to_background(col):
+    """whether some colour of the tables, plain or dimmed by the checker, gives the background's bytes at some light level k
+    in [AMBIENT, 1] -- with a level to spare on every channel for the kernel's float32: |255 a k - background| <= 1.5"""
+    rows = [col["shape_rgba"]] + ([col["env_shape_rgba"].reshape(-1, 4)] if "env_shape_rgba" in col else [])
+    a = np.concatenate(rows)[:, :3].astype(np.float64)
+    a = np.concatenate([a, sr.CHECKER_DIM * a])
+    bg = np.array(sr.BACKGROUND, dtype=np.float64)
+    lo, hi = ((bg - 1.5) / (255 * a)).max(axis=1), ((bg + 1.5) / (255 * a)).min(axis=1)
+    return bool((np.maximum(lo, sr.AMBIENT) <= np.minimum(hi, 1.0)).any())
+
+
 @pytest.mark.parametrize("kind,name,N", sc.all_configs())
 def test_kernel_matches_reference_on_the_case_tables(kind, name, N):
     case, col, ref = sc.build(kind, name, N), sc.colours(kind, name, N), sc.reference(kind, name, N)
+    assert not can_shade_to_background(col), "a surface of this case could carry the background colour: the second direction below would not hold"
     px = make_px(N)
     try:
         px.cuda_rigid_body_data.torch()[:] = torch.from_numpy(case["rigid"]).to(DEVICE)
@@ -64,6 +78,9 @@ def test_kernel_matches_reference_on_the_case_tables(kind, name, N):
             assert (flat[-GUARD:] == FILL).all(), "guard bytes were written"
             assert not (rgba == FILL).all(dim=-1).any(), "a pixel was left unwritten"
             compare(f"{kind} {name} N={N} camera {ci} ({W} x {H})", rgba.cpu().numpy(), ref[ci])
+            # one walk for both images: the background colour exactly where the depth camera hit nothing, and nowhere else
+            is_background = (rgba == torch.tensor(sr.BACKGROUND + (255,), dtype=torch.uint8, device=DEVICE)).all(dim=-1)
+            assert torch.equal(is_background, dep == 0), (kind, name, N, ci, (is_background != (dep == 0)).nonzero()[:4].tolist())
             rgba2, flat2 = guarded_rgba(N, H, W)
             px.raycast_shade(rid, ci, rgba2)
             assert torch.equal(flat2, first), "a second launch differs"
