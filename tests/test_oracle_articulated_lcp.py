@@ -18,7 +18,8 @@ from tests import oracle_backend as ob
 from tests.articulated_lcp_cases import A_PAD, DT, G, H, KP, N
 from tests.indep_dynamics import aba_forward_dynamics, link_point_jacobian, mass_matrix_and_bias, urdf_link_poses
 
-NAMES = list(cases.SCENES)
+NAMES = list(cases.SCENES)                                                     # every scene with a problem of its own
+ON_MESH = [n for n, (b, m) in cases.VARIANTS.items() if m == "ground"]         # same problem, ground contacts out of the triangle stage
 
 
 def check_complementarity(info):
@@ -31,12 +32,12 @@ _REFS = {}
 
 def references(sc):
     """the direct solution of every env of a scene, solved once per test session and left unchanged"""
-    if sc.name not in _REFS:
+    if sc.base not in _REFS:  # (a mesh variant shares its base scene's problem and entry)
         refs = [cases.reference(sc, e) for e in range(N)]
         for r in refs:
             check_complementarity(r["info"])
-        _REFS[sc.name] = refs
-    return _REFS[sc.name]
+        _REFS[sc.base] = refs
+    return _REFS[sc.base]
 
 
 # ---- mass_matrix_and_bias, the Jacobian ---------------------------------------------------------------------------------
@@ -168,6 +169,32 @@ def test_turntable_twist_closed_form(tmp_path):
     assert [r["v"][0][5] - r["qd"][0] > 1e-9 for r in references(sc)] == [False, False, False, True, True]
 
 
+def test_fetch_limits_rows_switch_on_one_after_the_other(tmp_path):
+    """torso (dof 3), right finger (13), left finger (14), each 0.2 mm from a limit with its target beyond: a row pushes iff the
+    joint's contact-free velocity (A^-1 rhs) exceeds C / dt, every such velocity is 10 % off that threshold, a pushing row leaves
+    its joint at exactly C / dt towards the limit (A couples the three to other joints, the rest is Lemke's)"""
+    sc = cases.make_scene("fetch_limits", tmp_path)
+    dofs, sign = (cases.FETCH_TORSO, cases.FETCH_R, cases.FETCH_L), np.array([1.0, -1.0, 1.0])
+    pushing = []
+    for e, r in enumerate(references(sc)):
+        pb = cases.problem(sc, e)
+        free = np.linalg.solve(pb["A"], pb["rhs"])
+        rows = {k: (s, C) for k, s, C in pb["limits"]}
+        on = []
+        for k, sg in zip(dofs, sign):
+            s, C = rows[k]
+            assert s == -sg and abs(C - 0.0002) < 2e-7, (k, s, C)  # (the row's sign is that of the limit's normal: away from it)
+            assert abs(sg * free[k] / (C / DT) - 1) > 0.1, (e, k, free[k], C / DT)
+            on.append(bool(sg * free[k] > C / DT))
+            assert abs(r["qd"][k] - (sg * C / DT if on[-1] else free[k])) < (1e-10 if on[-1] else 1e-3), (e, k, r["qd"][k])
+        lam = {pb["limits"][i][0]: x for i, x in enumerate(r["info"]["lam"][len(r["contacts"]):])}
+        assert [bool(lam[k] > 1e-9) for k in dofs] == on and not any(x > 1e-9 for k, x in lam.items() if k not in dofs)
+        pushing.append(on)
+    assert pushing == [[False, False, False], [True, False, False], [True, True, False], [True, True, False], [True, True, True]]
+    # the torso's drive is saturated in the last two envs (its row then holds a joint without implicit terms), no other drive is
+    assert [[k for k in range(15) if r["saturated"][k]] for r in references(sc)] == [[], [], [], [cases.FETCH_TORSO], [cases.FETCH_TORSO]]
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_solution_does_not_depend_on_the_covering_vector(name, tmp_path):
     """a scene must have ONE velocity solution: Lemke started from other covering vectors ends in the same place. So must
@@ -180,7 +207,7 @@ def test_solution_does_not_depend_on_the_covering_vector(name, tmp_path):
         for _ in range(2):
             other = cases.reference(sc, e, covering=rng.uniform(0.5, 2.0, n))
             check_complementarity(other["info"])
-            assert np.abs(other["qd"] - r["qd"]).max() < 1e-9 and np.abs(other["v"] - r["v"]).max() < 1e-9, (name, e)
+            assert np.abs(other["qd"] - r["qd"]).max() < 1e-9 and (not sc.frees or np.abs(other["v"] - r["v"]).max() < 1e-9), (name, e)
             for k, w in r["by_pair"].items():
                 d = other["by_pair"][k] - w
                 assert max(abs(d @ part) for part in cases.compared_parts(sc, e, r, k)) < 1e-9, (name, e, k, d)
@@ -277,13 +304,30 @@ def test_every_env_is_clear_of_its_thresholds(name, tmp_path):
 
 
 # ---- the oracle against the direct solution -----------------------------------------------------------------------------------
-def panda_alignment(sc):
-    """hand pointing down, pads axis-aligned, the pinch along y"""
-    T = urdf_link_poses(sc.robot, sc.q[0], cases._root_T(sc.root_p))
-    R = T["panda_hand"][:3, :3]
-    assert np.abs(R @ [0, 0, 1] - [0, 0, -1]).max() < 1e-6 and np.abs(np.abs(R) - np.abs(R).round()).max() < 1e-6
-    d = T["panda_leftfinger"][:3, 3] - T["panda_rightfinger"][:3, 3]
-    assert np.abs(np.abs(d) - [0, 2 * cases.W, 0]).max() < 1e-6
+def alignment(sc):
+    """of the scene's own links, in every env: each pad's box is axis-aligned in the world (its frame a signed permutation); two
+    pads that hold the same free body along an axis face each other along that axis and nowhere else (their link frames differ
+    along it alone, by the body's width plus the pads' own offsets); the Panda's and panda_stick's hand points down"""
+    for e in range(N):
+        T = urdf_link_poses(sc.robot, sc.q[e], cases._root_T(sc.root_p))
+        for link, s in sc.pads.items():
+            R = (T[link] @ cases._T44(s.pose))[:3, :3]
+            assert np.abs(np.abs(R) - np.abs(R).round()).max() < 1e-6 and np.abs(np.abs(R).round().sum(0) - 1).max() == 0, (sc.name, link, R)
+        if "panda_hand" in T:
+            assert np.abs(T["panda_hand"][:3, :3] @ [0, 0, 1] - [0, 0, -1]).max() < 1e-6
+        held = {}
+        for a, b, axis in sc.pairs:
+            for link, body in ((a, b), (b, a)):
+                if isinstance(link, str) and not isinstance(body, str) and body >= 0:
+                    held.setdefault((body, axis), []).append(link)
+        for (body, axis), links in held.items():
+            if len(links) == 2:
+                pa, pb = (T[l] @ cases._T44(sc.pads[l].pose) for l in links)
+                d = np.abs(pa[:3, 3] - pb[:3, 3])
+                width = 2 * sc.frees[body].half[axis] + sum((np.abs(X[:3, :3]).round() @ sc.pads[l].half_size)[axis] for l, X in zip(links, (pa, pb)))
+                want = np.zeros(3)
+                want[axis] = width
+                assert np.abs(d - want).max() < 1e-6, (sc.name, links, d, want)
 
 
 def sweeps_have_exited(sc, precision):
@@ -293,11 +337,12 @@ def sweeps_have_exited(sc, precision):
     return np.array_equal(a["qd"], b["qd"]) and np.array_equal(a["v"], b["v"])
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", cases.CASES)
 def test_f64_oracle_matches_direct_solution(name, tmp_path):
+    """every scene and every mesh variant: contact counts equal to the reference's points per pair (four per face, also where the
+    face lies on the one-triangle ground), velocities and impulses within the f64 bounds, the sweeps stopped by their tolerance"""
     sc = cases.make_scene(name, tmp_path)
-    if sc.urdf is None:
-        panda_alignment(sc)
+    alignment(sc)
     model = cases.compile_scene(sc)
     px = ob.make_system(model, N, precision="f64")
     got = cases.run_solver(px, sc, model)
@@ -305,11 +350,13 @@ def test_f64_oracle_matches_direct_solution(name, tmp_path):
     ev, ei = cases.errors(sc, model, got, references(sc))
     print(f"\nMEASURED_F64 {name}: velocity {ev:.3g} impulse {ei:.3g}")
     assert sweeps_have_exited(sc, "f64")
-    tol_v, tol_i = cases.TOL_F64.get(name, (cases.TOL_V_F64, cases.TOL_I_F64))
+    # (TOL_F64's two exceptions are of the first ten scenes; a mesh variant is its base scene's problem and is held to that scene's
+    # bound, slider_push's among them. No scene added since has an exception)
+    tol_v, tol_i = cases.TOL_F64.get(sc.base, (cases.TOL_V_F64, cases.TOL_I_F64))
     assert ev < tol_v and ei < tol_i, (ev, ei)
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + ON_MESH)
 def test_f32_oracle_matches_direct_solution(name, tmp_path):
     """the figures F32_ORACLE_ERROR holds are re-measured here: they must not have grown by more than a quarter (the kernel's
     bounds are 4 x the largest of a family; a figure that drifted would make them mean less)"""
@@ -325,13 +372,17 @@ def test_f32_oracle_matches_direct_solution(name, tmp_path):
 
 
 # ---- references broken on purpose -------------------------------------------------------------------------------------------
+# jacobian_sign flips the last joint's column where the pad's rows have one (branch_arm: the slide j3); else the last joint on the
+# pad's path to the base with a column that counts: panda_stick's joint 6 (the push passes by joint 7's axis at 0.015 m), the
+# Fetch's torso under the torso pad
+FLIPPED_JOINT = {"stick_drag": 5, "fetch_ground_press": 3}
 def broken_reference(sc, env, how):
     """the direct solution of a problem with one row type written wrongly"""
     pb = dict(cases.problem(sc, env))
-    if how == "jacobian_sign":               # the sign of a link's Jacobian column (the last joint's)
+    if how == "jacobian_sign":               # the sign of a link's Jacobian column (the last joint's, unless that one's is zero)
         jac = pb["jac"]
         flip = np.ones(len(pb["rhs"]))
-        flip[-1] = -1.0
+        flip[FLIPPED_JOINT.get(sc.base, -1)] = -1.0
         pb["jac"] = lambda link, x: tuple(J * flip for J in jac(link, x))
     elif how == "tendon_diagonal_only":      # the tendon's off-diagonal dropped from A
         pb["A"] = pb["A"] - sum((DT * DT * k + DT * d) * (np.outer(cc, cc) - np.diag(cc * cc)) for cc, o_, k, d in pb["tendons"])
@@ -348,6 +399,11 @@ def broken_reference(sc, env, how):
 BREAKS = [
     ("jacobian_sign", "level_arm_press"),
     ("jacobian_sign", "panda_pinch_tendon"),
+    ("jacobian_sign", "fetch_pinch"),            # (the last joint: the left finger's own column)
+    ("jacobian_sign", "fetch_ground_press"),
+    ("jacobian_sign", "stick_drag"),
+    ("jacobian_sign", "branch_arm_two_cubes"),
+    ("jacobian_sign", "level_arm_press_on_mesh"),
     ("tendon_diagonal_only", "panda_pinch_tendon"),
     ("saturated_keeps_implicit", "two_pad_hold"),
     ("torsion_one_point", "turntable_twist"),
