@@ -273,6 +273,46 @@ typedef struct mssim_plug_task {
 
 int mssim_task_plug_outputs(mssim_handle h, const mssim_plug_task* task, float* obs, float* reward, uint8_t* flags, float* metrics, void* stream);
 
+/* DrawTriangle-style dot layer + evaluate + state observation in one launch (envs/tasks/tabletop/draw_triangle.py). The
+ * drawing is no set of bodies: it is the env's own device tables, which this call updates IN PLACE (update != 0) before it
+ * evaluates them. Per env, with k = draw_step[e]:
+ *   update and k < max_dots:
+ *     drawn = tcp.z < z_thresh (strict; false for a NaN)
+ *     dots[e][k] = drawn ? (tcp.x, tcp.y) : (0, 0)
+ *     hit_p = drawn and dx * dx + dy * dy < near_thresh2 (each product and the sum rounded to float32; strict), for every
+ *             reference point p < n_ref of triangles[e]
+ *     dot_near[e][k] = drawn ? (any hit_p ? 1 : 0) : -1;  ref_hit[e][p] |= hit_p;  draw_step[e] = k + 1
+ *   update and k >= max_dots: nothing is written to the tables and the counter stays (a step past the table draws nothing)
+ *   success = no dot_near[e][i] == 0 for i < max_dots (every drawn dot is near) and every ref_hit[e][p], p < n_ref
+ * so an env with nothing drawn fails on its unhit reference points, and a NaN tcp position draws nothing or a dot that is
+ * not near: never a success of its own making, and no other env is touched. update == 0 (a reset's outputs) reads only.
+ * obs [N][2*n_dof+35] f32 (qpos, qvel, tcp_pose7, goal_pose7, vertices - tcp.p 9, goal_pos3, vertices 9),
+ * reward [N] f32 = success * reward_scale (1: sparse, 0: none), flags [N][1] u8 = success.
+ * The reference points of an env are spread over the 16 lanes that serve it and reduced with a ballot; no atomics, plain
+ * vector stores. Like the seven tasks above, this one never runs at the control-step kernel's tail.
+ * Refused (rc 3): a missing table, max_dots that is not a positive multiple of 4, n_ref <= 0, dot_near not 4-byte aligned. */
+typedef struct mssim_draw_task {
+  int32_t tcp_row, goal_row;  /* rigid_body_data body rows */
+  const float* vertices;      /* device [N][3][3]: the goal triangle's corners in the env frame; required */
+  const float* triangles;     /* device [N][n_ref][2]: the reference points of the outline; required */
+  float* dots;                /* device [N][max_dots][2], in place; required */
+  int8_t* dot_near;           /* device [N][max_dots] -1 / 0 / 1, in place; required, 4-byte aligned */
+  uint8_t* ref_hit;           /* device [N][n_ref] 0 / 1, in place; required */
+  int32_t* draw_step;         /* device [N]: dots appended so far, in place; required */
+  int32_t max_dots, n_ref;    /* 300, 153 */
+  float z_thresh;             /* 0.028 m */
+  float near_thresh2;         /* 0.025^2 m^2 */
+  int32_t update;             /* 1: append this step's dot first; 0: outputs of the tables as they are */
+  float reward_scale;
+  int32_t* elapsed_steps;     /* optional, as in mssim_pick_task */
+  int32_t* elapsed_out;
+  uint8_t* truncated_out;     /* optional device [N]: new elapsed_steps >= time_limit */
+  int32_t time_limit;
+  uint8_t* terminated_out;    /* optional device [N]: a copy of success */
+} mssim_draw_task;
+
+int mssim_task_draw_outputs(mssim_handle h, const mssim_draw_task* task, float* obs, float* reward, uint8_t* flags, void* stream);
+
 /* The robot-dependent rules of the task epilogues, stored on the handle: what "the robot is static" means and how many
  * joints the velocity norm of PickCube's static reward covers. With no profile set (or after a NULL / n_ranges == 0 call)
  * every epilogue applies the Panda's rules from its own task struct, as before: static = max |qvel[:n_static_dofs]| <=
@@ -437,6 +477,24 @@ int mssim_raycast_render(mssim_handle h, int32_t id, int32_t camera, int16_t* po
  * aligned. Refused: a bad id or camera, shading before any colours were set, a misaligned or missing output. */
 int mssim_raycast_set_colours(mssim_handle h, int32_t id, const float* shape_rgba, const float* env_shape_rgba);
 int mssim_raycast_shade(mssim_handle h, int32_t id, int32_t camera, uint8_t* rgba_u8, void* stream);
+
+/* ---- A dot layer composited over a shaded view: the drawing of DrawTriangle-style tasks ---------------------------
+ * The dots are no shapes of the scene: they are an env's table of xy positions (mssim_draw_task). One launch over the
+ * RGBA picture of mssim_raycast_shade: a pixel's ray meets the horizontal plane z = `z` of the env frame at parameter t
+ * (the z-depth, as above); where t >= near, the point lies within `radius` of a drawn dot (dot_near[e][i] >= 0,
+ * i < min(count[e], max_dots)) and nothing of the scene is more than 1 mm nearer (depth_f32 of mssim_raycast_render for the
+ * same scene, camera and state: 0 = nothing, else t <= depth + 1e-3), the pixel becomes `rgba`; every other pixel keeps
+ * what it had. One 4-byte store per painted pixel, no atomics. Refused: a bad id or camera, a missing table or buffer,
+ * max_dots outside [1, 1024], a misaligned picture. */
+typedef struct mssim_dot_layer {
+  const float* dots;        /* device [N][max_dots][2] */
+  const int8_t* dot_near;   /* device [N][max_dots]: < 0 = not drawn */
+  const int32_t* count;     /* device [N]: table entries in use */
+  int32_t max_dots;
+  float z, radius;          /* plane height and disc radius, metres */
+  uint32_t rgba;            /* r | g << 8 | b << 16 | a << 24 */
+} mssim_dot_layer;
+int mssim_raycast_draw_dots(mssim_handle h, int32_t id, int32_t camera, const mssim_dot_layer* layer, const float* depth_f32, uint8_t* rgba_u8, void* stream);
 
 #ifdef __cplusplus
 }

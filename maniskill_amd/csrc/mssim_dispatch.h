@@ -7,10 +7,10 @@
 namespace mssim_dispatch {
 
 // TASK: 0 = plain control step; else the copy-out + that task's epilogue at the kernel's tail. kRoll, kPull, kPoke,
-// kLiftPeg, kPlace, kPullTool and kPlug have no row in kTails: their epilogue is always a launch of its own, tail_step() answers
-// kNone for them (kPoke and kPullTool on the two-row plain step, the other five on the one-row one).
+// kLiftPeg, kPlace, kPullTool, kPlug and kDraw have no row in kTails: their epilogue is always a launch of its own, tail_step() answers
+// kNone for them (kPoke and kPullTool on the two-row plain step, the other six on the one-row one; kDraw steps with <7, 0, false, 1>).
 enum Task { kPlain = 0, kPick = 1, kPush = 2, kPeg = 3, kStack = 4, kPushT = 5, kRoll = 6, kPull = 7, kPoke = 8, kLiftPeg = 9, kPlace = 10, kPullTool = 11,
-            kPlug = 12, kNumTasks = 13 };
+            kPlug = 12, kDraw = 13, kNumTasks = 14 };
 
 struct Key {
   int ndof;  // joints unrolled at compile time (9: the Panda, 7: panda_stick, 15: the Fetch), 0 = any topology

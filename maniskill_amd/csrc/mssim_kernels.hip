@@ -1250,6 +1250,95 @@ __global__ __launch_bounds__(256) void k_task_plug(DevModel M, DevState S, mssim
   task_plug_env(M, S, B, T, obs, reward, flags, metrics, e);
 }
 
+// DrawTriangle dot layer / evaluate / obs (draw_triangle.py _after_control_step, evaluate, _get_obs_extra; the rules are
+// stated at mssim_draw_task). The drawing is the env's own tables, updated in place: with T.update the dot of this control
+// step is appended at index draw_step[e] before the tables are evaluated; a counter at max_dots appends nothing.
+// 16 lanes per env, all 64 lanes of a wave call this (the ballots): lane c takes the reference points c, c + 16, ... against
+// the new dot, the words c, c + 16, ... of the env's dot_near row (four dots a word; a zero byte is a drawn dot away from
+// the outline) and the observation floats c, c + 16, ...; three ballots give the env's any / all. The tables are read before
+// the ballots and written after them, lane 0 writing the dot. `live`: the group has an env. No atomics, no LDS.
+MS_DEV void task_draw_env(const DevModel& M, const DevState& S, const mssim_buffers& B, const mssim_draw_task& T,
+                          float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags, int e, int c, bool live) {
+  const int N = S.N;
+  const int n = M.n_dof;
+  const int shift = (int)(threadIdx.x & 48u);  // the group's 16 bits of a ballot
+  const float* tcp = B.rigid_body_data + 13 * ((size_t)T.tcp_row * N + (live ? e : 0));
+  float tx = 0.f, ty = 0.f;
+  int k = 0;
+  bool append = false, drawn = false, any_hit = false, all_ref = true, none_far = true;
+  if (live) {
+    tx = tcp[0]; ty = tcp[1];
+    k = T.draw_step[e];
+    append = T.update != 0 && k >= 0 && k < T.max_dots;
+    drawn = append && tcp[2] < T.z_thresh;
+    const float* tri = T.triangles + 2 * (size_t)e * T.n_ref;
+    uint8_t* rh = T.ref_hit + (size_t)e * T.n_ref;
+    for (int p = c; p < T.n_ref; p += 16) {
+      bool hit;
+      {
+#pragma clang fp contract(off)  // (the torch path rounds both products and the sum)
+        const float dx = tx - tri[2 * p], dy = ty - tri[2 * p + 1];
+        hit = drawn && dx * dx + dy * dy < T.near_thresh2;
+      }
+      const bool was = rh[p] != 0;
+      if (hit && !was) rh[p] = 1;  // (a byte no other lane reads or writes)
+      any_hit = any_hit || hit;
+      all_ref = all_ref && (hit || was);
+    }
+    const uint32_t* dn = reinterpret_cast<const uint32_t*>(T.dot_near + (size_t)e * T.max_dots);
+    for (int w = c; w < (T.max_dots >> 2); w += 16) {
+      uint32_t v = dn[w];
+      if (append && w == (k >> 2)) v |= 0xffu << (8 * (k & 3));  // (the slot this call writes: judged by its new value below)
+      none_far = none_far && ((v - 0x01010101u) & ~v & 0x80808080u) == 0u;
+    }
+  }
+  const bool near = ((__ballot(any_hit) >> shift) & 0xffffull) != 0ull;
+  const bool refs = ((__ballot(all_ref) >> shift) & 0xffffull) == 0xffffull;
+  const bool dots_ok = ((__ballot(none_far) >> shift) & 0xffffull) == 0xffffull;
+  if (!live) return;
+  const bool success = refs && dots_ok && !(drawn && !near);
+  if (c == 0) {
+    if (append) {
+      const size_t at = (size_t)e * T.max_dots + k;
+      T.dots[2 * at] = drawn ? tx : 0.f; T.dots[2 * at + 1] = drawn ? ty : 0.f;
+      T.dot_near[at] = drawn ? (near ? 1 : 0) : -1;
+      T.draw_step[e] = k + 1;
+    }
+    reward[e] = success ? T.reward_scale : 0.f;
+    flags[e] = success;
+    if (T.terminated_out) T.terminated_out[e] = success;
+    if (T.elapsed_steps) { const int v = T.elapsed_steps[e] + 1; T.elapsed_steps[e] = v; if (T.elapsed_out) T.elapsed_out[e] = v; if (T.truncated_out) T.truncated_out[e] = v >= T.time_limit ? 1 : 0; }
+  }
+  const float* gl = B.rigid_body_data + 13 * ((size_t)T.goal_row * N + e);
+  const float* vt = T.vertices + 9 * (size_t)e;
+  float* o = obs + (size_t)e * (2 * n + 35);
+  for (int i = c; i < 2 * n + 35; i += 16) {
+    const int j = i - 2 * n;
+    float v;
+    if (i < n) v = B.art_qpos[(size_t)e * n + i];
+    else if (j < 0) v = B.art_qvel[(size_t)e * n + i - n];
+    else if (j < 7) v = tcp[j];
+    else if (j < 14) v = gl[j - 7];
+    else if (j < 23) v = vt[j - 14] - tcp[(j - 14) % 3];
+    else if (j < 26) v = gl[j - 23];
+    else v = vt[j - 26];
+    o[i] = v;
+  }
+}
+// COPYOUT: the launch first performs mssim_fetch(what) for its 64 envs (fetch_in_block). Either way 256 threads per block:
+// wave w serves the envs 16 w .. 16 w + 15 of the block's 64, four at a time
+template <bool COPYOUT>
+__global__ __launch_bounds__(256) void k_task_draw(DevModel M, DevState S, mssim_buffers B, unsigned what, mssim_draw_task T,
+                                                    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ flags) {
+  if (COPYOUT) (void)fetch_in_block(M, S, B, what);  // (ends with the block's barrier: every lane sees the rows)
+  const int first = xcd_chunk(blockIdx.x, gridDim.x) * 64 + 16 * (int)(threadIdx.x >> 6);
+  for (int it = 0; it < 4; it++) {
+    if (first + 4 * it >= S.N) break;  // (wave-uniform)
+    const int e = first + 4 * it + (int)((threadIdx.x & 63u) >> 4);
+    task_draw_env(M, S, B, T, obs, reward, flags, e, (int)(threadIdx.x & 15u), e < S.N);
+  }
+}
+
 // PushT pseudo-render (push_t.py pseudo_render_intersection): every template pixel (i, j) of the block's T, at its uv
 // grid centre (U[j], V[i], 1), is mapped by world_to_goal @ tee_to_world, divided by the third row, scaled to pixel
 // indices and truncated toward zero (.long()); an index outside [0, 64) sends the pixel to (0, 0). Index pair (x, y)
@@ -1991,7 +2080,7 @@ static int finger_pair_list(mssim_handle h, int obj_row, int f1_row, int f2_row)
   return 0;
 }
 
-// A task epilogue, the one sequence behind the twelve mssim_task_*_outputs. Refusals come first and leave what is owed owed.
+// A task epilogue, the one sequence behind the thirteen mssim_task_*_outputs. Refusals come first and leave what is owed owed.
 // An owed step_action + an owed fetch + the epilogue = ONE launch of the control-step kernel, where mssim_create found an
 // instance with the task's tail for the model (h->tail_fn). Otherwise what is owed is performed and the epilogue is a launch
 // of its own: `standalone(std::true_type, what, st)` launches k_task_*<true>, which first performs the owed copy-out `what`,
@@ -2018,7 +2107,7 @@ static int task_refusals(mssim_handle h, const TaskCall& c, const int (&rows)[NR
   return 0;
 }
 // The tail-less path, for a task without a member in the tail_task union (RollBall, PullCube, PokeCube, LiftPegUpright, PlaceSphere,
-// PullCubeTool, PlugCharger: h->tail_fn[c.id] is null for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
+// PullCubeTool, PlugCharger, DrawTriangle: h->tail_fn[c.id] is null for every model): an owed step_action runs as the plain control step, the epilogue is always a launch of its own.
 template <size_t NROWS, class Standalone>
 static int task_outputs(mssim_handle h, const TaskCall& c, const int (&rows)[NROWS], hipStream_t st, Standalone standalone) {
   if (int rc = task_refusals(h, c, rows)) return rc;
@@ -2191,6 +2280,19 @@ int mssim_task_plug_outputs(mssim_handle h, const mssim_plug_task* task, float* 
   });
 }
 
+int mssim_task_draw_outputs(mssim_handle h, const mssim_draw_task* task, float* obs, float* reward, uint8_t* flags, void* stream) {
+  const int rows[] = {task->tcp_row, task->goal_row};
+  const bool ok = task->vertices && task->triangles && task->dots && task->dot_near && task->ref_hit && task->draw_step && task->max_dots > 0 &&
+                  task->max_dots % 4 == 0 && task->n_ref > 0 && ((uintptr_t)task->dot_near & 3u) == 0;
+  const TaskCall call{mssim_dispatch::kDraw, "draw", ok ? nullptr : "task_draw_outputs: needs the vertices, the reference points and the four dot tables (device), max_dots a "
+                      "positive multiple of 4, n_ref > 0 and dot_near 4-byte aligned", /*pair_rows=*/nullptr, obs, reward, flags, /*extra=*/nullptr};
+  return task_outputs(h, call, rows, (hipStream_t)stream, [&](auto fetch, unsigned what, hipStream_t st) {
+    // 64 envs a block in both forms: four waves of 16 lanes per env
+    hipLaunchKernelGGL(k_task_draw<decltype(fetch)::value>, env_grid(h->N, 64), dim3(256), 0, st,
+                       h->M, h->S, h->buf, what, *task, obs, reward, flags);
+  });
+}
+
 int64_t mssim_tail_step_count(mssim_handle h) { return h ? h->n_tail_steps : -1; }
 
 int mssim_set_task_robot(mssim_handle h, const mssim_task_robot* robot) {
@@ -2284,6 +2386,7 @@ int mssim_overflow_count(mssim_handle h, void* stream) {
 #include "mssim_raycast_desc.h"  // what mssim_raycast_create accepts (host only)
 #include "mssim_raycast.h"       // the ray caster of the camera observations: k_raycast and the mssim_raycast_* entry points
 #include "mssim_raycast_shade.h" // its flat-shaded view for render(): k_raycast_shade, mssim_raycast_set_colours / _shade
+#include "mssim_raycast_dots.h"  // a dot layer composited over that view: k_raycast_dots, mssim_raycast_draw_dots
 #include "mssim_test_collide.h"  // test hook, not part of the ABI: the manifold routines of k_solve16 on explicit shape pairs
 
 #ifdef MSSIM_PHASE_CLOCKS

@@ -801,7 +801,11 @@ class BaseEnv(gym.Env):
             self._check_render_budget(cam)
         for cam in cameras.values():
             cam.capture_picture()
+            self._picture_overlay(cam)
         return [cam.get_picture() for cam in cameras.values()]
+
+    def _picture_overlay(self, camera: Camera):
+        """a task's own layer over a camera's shaded view, painted after the scene (DrawTriangle's dots); nothing by default"""
 
     def render_rgb_array(self, camera_name: Optional[str] = None) -> torch.Tensor:
         """uint8 [N, H', W', 3]: the human render cameras' shaded views, tiled (one of them by name). Hidden objects

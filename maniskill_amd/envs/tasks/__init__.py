@@ -1,3 +1,3 @@
-from .tabletop import (LiftPegUprightEnv, PegInsertionSideEnv, PickCubeEnv, PlaceSphereEnv, PlugChargerEnv, PokeCubeEnv, PullCubeEnv, PullCubeToolEnv, PushCubeEnv, PushTEnv,
+from .tabletop import (DrawTriangleEnv, LiftPegUprightEnv, PegInsertionSideEnv, PickCubeEnv, PlaceSphereEnv, PlugChargerEnv, PokeCubeEnv, PullCubeEnv, PullCubeToolEnv, PushCubeEnv, PushTEnv,
                        RollBallEnv, StackCubeEnv)
 from .empty_env import EmptyEnv

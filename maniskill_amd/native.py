@@ -222,6 +222,20 @@ class PlugTask(C.Structure):
                 ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
 
 
+class DrawTask(C.Structure):
+    """mssim_draw_task of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("tcp_row", C.c_int32), ("goal_row", C.c_int32), ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("dots", C.c_void_p),
+                ("dot_near", C.c_void_p), ("ref_hit", C.c_void_p), ("draw_step", C.c_void_p), ("max_dots", C.c_int32), ("n_ref", C.c_int32),
+                ("z_thresh", C.c_float), ("near_thresh2", C.c_float), ("update", C.c_int32), ("reward_scale", C.c_float),
+                ("elapsed_steps", C.c_void_p), ("elapsed_out", C.c_void_p), ("truncated_out", C.c_void_p), ("time_limit", C.c_int32), ("terminated_out", C.c_void_p)]
+
+
+class DotLayer(C.Structure):
+    """mssim_dot_layer of include/mssim_hip_tasks.h (HIP library only)"""
+    _fields_ = [("dots", C.c_void_p), ("dot_near", C.c_void_p), ("count", C.c_void_p), ("max_dots", C.c_int32), ("z", C.c_float), ("radius", C.c_float),
+                ("rgba", C.c_uint32)]
+
+
 class TaskRobot(C.Structure):
     """mssim_task_robot of include/mssim_hip_tasks.h (HIP library only): the robot-dependent rules of the task epilogues"""
     _fields_ = [("n_ranges", C.c_int32), ("first", C.c_int32 * 2), ("count", C.c_int32 * 2), ("thresh", C.c_float * 2),
@@ -342,6 +356,8 @@ class NativeLib:
             ("task_place_outputs", C.c_int, [H, C.POINTER(PlaceTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_pulltool_outputs", C.c_int, [H, C.POINTER(PullToolTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
             ("task_plug_outputs", C.c_int, [H, C.POINTER(PlugTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("task_draw_outputs", C.c_int, [H, C.POINTER(DrawTask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            ("raycast_draw_dots", C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(DotLayer), C.c_void_p, C.c_void_p, C.c_void_p]),
             ("tail_step_count", C.c_int64, [H]),
             ("set_task_robot", C.c_int, [H, C.POINTER(TaskRobot)]),
             ("set_ee_ik_map", C.c_int, [H, C.POINTER(EeIkMap), C.c_void_p]),
@@ -545,6 +561,16 @@ class NativeSim:
         if self.lib.task_plug_outputs is None:
             raise NativeError(f"{self.lib.path} has no task_plug_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
         self._check(self.lib.task_plug_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, metrics_ptr, stream), "task_plug_outputs")
+
+    def task_draw_outputs(self, task: "DrawTask", obs_ptr, reward_ptr, flags_ptr, stream=None):
+        if self.lib.task_draw_outputs is None:
+            raise NativeError(f"{self.lib.path} has no task_draw_outputs (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.task_draw_outputs(self.h, C.byref(task), obs_ptr, reward_ptr, flags_ptr, stream), "task_draw_outputs")
+
+    def raycast_draw_dots(self, rid: int, camera: int, layer: "DotLayer", depth_ptr, rgba_ptr, stream=None):
+        if self.lib.raycast_draw_dots is None:
+            raise NativeError(f"{self.lib.path} has no raycast_draw_dots (an extra of the HIP library, include/mssim_hip_tasks.h)")
+        self._check(self.lib.raycast_draw_dots(self.h, int(rid), int(camera), C.byref(layer), depth_ptr, rgba_ptr, stream), "raycast_draw_dots")
 
     def tail_step_count(self) -> int:
         """control steps that ran with the task epilogue at the control-step kernel's tail (HIP library only)"""

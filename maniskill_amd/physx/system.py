@@ -434,6 +434,11 @@ class MssimSystem:
         required; `task.goal_pose` points at the env's stored goal tensor (include/mssim_hip_tasks.h; HIP library only)"""
         self._sim.task_plug_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), None if metrics is None else metrics.data_ptr(), self._stream())
 
+    def task_draw_outputs(self, task, obs: torch.Tensor, reward: torch.Tensor, flags: torch.Tensor):
+        """DrawTriangle dot layer / evaluate / obs in one launch; the struct points at the env's dot tables, which the
+        launch updates in place where `task.update` is set (include/mssim_hip_tasks.h; HIP library only)"""
+        self._sim.task_draw_outputs(task, obs.data_ptr(), reward.data_ptr(), flags.data_ptr(), self._stream())
+
     # ------------------------------------------------------------------ ray-cast cameras (HIP only)
     def raycast_create(self, scene_arrays: dict, cameras: Sequence[dict]) -> int:
         """a ray-cast scene (`model.compile.raycast_scene`) with its cameras -> id for `raycast_render`
@@ -488,6 +493,18 @@ class MssimSystem:
         w, h = sizes[camera]
         assert rgba.dtype == torch.uint8 and rgba.is_contiguous() and tuple(rgba.shape) == (self.num_envs, h, w, 4)
         self._sim.raycast_shade(rid, camera, rgba.data_ptr(), self._stream())
+
+    def raycast_draw_dots(self, rid: int, camera: int, layer, depth: torch.Tensor, rgba: torch.Tensor):
+        """one launch on the current stream: the discs of a dot layer (`native.DotLayer`: an env's table of drawn dots)
+        painted over the shaded view `rgba` uint8 [N, H, W, 4] of `raycast_shade`, hidden where `depth` f32 [N, H, W] of
+        `raycast_render` for the same camera and state has something nearer"""
+        sizes = self._raycast_sizes(rid)
+        if not 0 <= camera < len(sizes):
+            raise native.NativeError(f"raycast_draw_dots: scene {rid} has no camera {camera} (it has {len(sizes)})")
+        w, h = sizes[camera]
+        assert rgba.dtype == torch.uint8 and rgba.is_contiguous() and tuple(rgba.shape) == (self.num_envs, h, w, 4)
+        assert depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (self.num_envs, h, w)
+        self._sim.raycast_draw_dots(rid, camera, layer, depth.data_ptr(), rgba.data_ptr(), self._stream())
 
     def raycast_destroy(self, rid: int):
         self._raycast_sizes(rid)

@@ -126,6 +126,19 @@ class RaycastRig:
             camera._rgba = torch.zeros((self.scene.num_envs, camera.height, camera.width, 4), dtype=torch.uint8, device=self.scene.device)
         px.raycast_shade(rid, camera._index, camera._rgba)
 
+    def draw_dots(self, camera: "Camera", layer):
+        """a dot layer (`native.DotLayer`) painted over the camera's shaded view, after `shade`: one ray-cast launch for this
+        scene's float depth (what hides a dot), one compositing launch. The camera's position / segmentation buffer is
+        overwritten on the way, as by a capture."""
+        px, rid = self.scene.px, self._create()
+        assert camera._rgba is not None, f"{camera.uid}: capture_picture() first"
+        if camera._depth is None:
+            camera._depth = torch.zeros((self.scene.num_envs, camera.height, camera.width), dtype=torch.float32, device=self.scene.device)
+        if camera._pos_seg is None:
+            camera._pos_seg = torch.zeros((self.scene.num_envs, camera.height, camera.width, 4), dtype=torch.int16, device=self.scene.device)
+        px.raycast_render(rid, camera._index, camera._pos_seg, camera._depth)
+        px.raycast_draw_dots(rid, camera._index, layer, camera._depth, camera._rgba)
+
     def render(self, camera: "Camera"):
         px = self.scene.px
         self._create()
@@ -163,6 +176,7 @@ class Camera:
         assert len(self._local) in (1, N), f"{cfg.uid}: one pose, or one per env"
         self._pos_seg = None  # int16 [N, H, W, 4], allocated at the first capture
         self._rgba = None     # uint8 [N, H, W, 4], allocated at the first picture
+        self._depth = None    # float32 [N, H, W], allocated at the first picture with a dot layer
         self._rig = rig
         self._index = rig.add(self) if rig is not None else None
 
@@ -187,6 +201,10 @@ class Camera:
     def capture_picture(self):
         """one shading launch on the current stream, from the pose buffers as they are: the flat-shaded view"""
         self._rig.shade(self)
+
+    def draw_dots(self, layer):
+        """paints a dot layer over the picture of the last `capture_picture` (`RaycastRig.draw_dots`)"""
+        self._rig.draw_dots(self, layer)
 
     def get_picture(self) -> torch.Tensor:
         """uint8 [N, H, W, 3]: the shaded view of the last `capture_picture`, a VIEW of the camera's RGBA buffer (the next

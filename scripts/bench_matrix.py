@@ -67,6 +67,10 @@ for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("Pe
                  # millimetre geometry: 1.5 mm pegs and a five-box receptacle (one row; the epilogue reads the env's stored goal).
                  # `plug` selects this row alone and runs it twice in one process: native, then MS_FUSED=0 (the torch epilogue)
                  (("PlugCharger-v1", 4096), {}),
+                 # panda_stick on a canvas: the plain one-row step <7, 0> (4 position sweeps, no velocity sweep) + the dot layer /
+                 # evaluate epilogue. `draw` selects this row alone and runs it twice as `plug` does. The unreset 1000 steps run
+                 # past the 300-dot table: from step 300 on the epilogue appends nothing
+                 (("DrawTriangle-v1", 4096), {}),
                  (("PickCube-v1", 4096), dict(sim_config=dict(control_freq=25))),  # 4 substeps (SURVEY 8d reports 5 and 4)
                  # BASELINE config 5's robot and env count: the Fetch on an empty ground, and in synthetic triangle-mesh rooms
                  (("Empty-v1", 1024), dict(robot_uids="fetch")), (("SceneManipulation-v1", 1024), dict(build_config_idxs=[i % 5 for i in range(1024)])),
@@ -84,7 +88,7 @@ for args, kw in ((("PickCube-v1", 4096), {}), (("PushCube-v1", 4096), {}), (("Pe
     if fetch_tabletop and "fetch_tabletop" in only:
         run(*args, **kw)
         continue
-    if "plug" in only and args[0] == "PlugCharger-v1":
+    if ("plug" in only and args[0] == "PlugCharger-v1") or ("draw" in only and args[0] == "DrawTriangle-v1"):
         before = os.environ.get("MS_FUSED")
         for fused in ("1", "0"):  # (read when the env is made; each line's `fused` says which path ran)
             os.environ["MS_FUSED"] = fused

@@ -15,6 +15,7 @@ run PegInsertionSide-v1 2048 3000 pd_joint_delta_pos
 run PlaceSphere-v1 4096 2000 pd_joint_delta_pos
 run PullCubeTool-v1 4096 2000 pd_joint_delta_pos
 run PlugCharger-v1 4096 2000 pd_joint_delta_pos
+run DrawTriangle-v1 4096 2000 pd_joint_delta_pos
 MS_ROBOT=fetch run Empty-v1 1024 2000 pd_joint_delta_pos
 MS_ROBOT=fetch run Empty-v1 1024 2000 pd_ee_delta_pos
 MS_ROBOT=fetch run Empty-v1 1024 2000 pd_ee_delta_pose
